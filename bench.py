@@ -3,7 +3,7 @@
 % of the HBM roofline for per-channel int8 symmetric requantization of
 4096x4096 FP32 weight buffers (BASELINE config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A *step* is one pass of the hot path over one batch: ONE launch of
@@ -13,8 +13,13 @@ served from cache). Multi-GPU shards whole tensor-buffers: every rank owns its
 own pool (weak scaling, no collective on the data path).
 
 One JSON line is printed by rank 0 (contract in the task statement) with
-`roofline` (dominant kernel, HIP-event timed) and `cpu_baseline` (the NumPy
-oracle timed on the host, baseline only).
+`roofline` (dominant kernel, HIP-event timed over the K timed launches).
+
+A plain run does only what that line's headline needs: set up, warm up, time
+the K steps, write the outputs (--dump-outputs) and print. --full adds what
+takes runs of its own: `cpu_baseline` (the NumPy oracle timed on the host),
+the launch percentiles topped up to PCT_LAUNCHES launches, `extras` (the other
+BASELINE configurations and kernels at their rooflines) and `sharded`.
 """
 import argparse
 import json
@@ -49,10 +54,43 @@ def parse():
                  help="ranks = GPUs of this node; a plain `python bench.py --gpus N` starts the N ranks itself")
   p.add_argument("--steps", type=int, default=200)
   p.add_argument("--warmup", type=int, default=20)
-  p.add_argument("--cpu-seconds", type=float, default=10.0,
-                 help="target CPU time for the cpu_baseline sample (0 disables)")
-  p.add_argument("--extras", type=int, default=1, help="also time configs 3 / int4 (untimed region)")
-  return p.parse_args()
+  p.add_argument("--full", action="store_true",
+                 help="also measure what the headline does not need: cpu_baseline, launch percentiles over"
+                      f" {PCT_LAUNCHES} launches, extras and the sharded configurations (untimed region)")
+  p.add_argument("--cpu-seconds", type=float, default=None,
+                 help="target CPU time for the cpu_baseline sample (0 disables; default 10 with --full, else 0)")
+  p.add_argument("--extras", type=int, default=None,
+                 help="also time the other configurations (untimed region; default 1 with --full, else 0)")
+  p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                 help="write what the last timed step computed to DIR/<name>.npy (float32; see dump_outputs)")
+  args = p.parse_args()
+  if args.cpu_seconds is None:
+    args.cpu_seconds = 10.0 if args.full else 0.0
+  if args.extras is None:
+    args.extras = 1 if args.full else 0
+  return args
+
+
+DUMP_ROWS = 128   # rows of every buffer's q that --dump-outputs writes (the whole q of a step is 256 MiB)
+
+
+def dump_outputs(batch, outdir: str) -> None:
+  """What the timed path hands its caller after its last step, as float32 .npy files under `outdir` (34 MB in all):
+    scale.npy  [POOL, ROWS]             every buffer's per-channel scale, whole
+    q_rows.npy [POOL, DUMP_ROWS, COLS]  the int8 values of DUMP_ROWS rows of every buffer, the same rows in each: a
+                                        fixed sample, np.random.default_rng(0).choice(ROWS, DUMP_ROWS, replace=False), sorted
+  The inputs come from a generator seeded with 1234 + rank, so two builds run with the same arguments can be compared
+  file by file."""
+  import numpy as np
+  import torch
+  os.makedirs(outdir, exist_ok=True)
+  rows = np.sort(np.random.default_rng(0).choice(ROWS, DUMP_ROWS, replace=False))
+  idx = torch.from_numpy(rows).to(batch.q[0].device)
+  torch.cuda.synchronize()
+  out = {"scale": torch.stack(batch.scale).float().cpu().numpy(),
+         "q_rows": torch.stack([q.index_select(0, idx) for q in batch.q]).float().cpu().numpy()}
+  for name, a in out.items():
+    np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def cpu_baseline(seconds: float):
@@ -787,11 +825,14 @@ def main():
   launch_sorted = sorted(a.elapsed_time(b) for a, b in pairs)
   kern_ms = sum(launch_sorted) / len(launch_sorted)
   achieved = POOL * ALG_BYTES / (kern_ms * 1e-3) / 1e9
+  if args.dump_outputs and rank == 0:
+    dump_outputs(batch, args.dump_outputs)
   # SURVEY 8d asks for the percentiles of >= 100 launches; the driver's --steps may be 20. The step's work is never
-  # changed: when K < PCT_LAUNCHES the same launch is repeated AFTER the timed region until that many event pairs
-  # exist, and the percentiles are taken over all of them (`launch_ms` / `achieved` stay the mean of the K timed ones).
+  # changed: with --full and K < PCT_LAUNCHES the same launch is repeated AFTER the timed region until that many event
+  # pairs exist, and the percentiles are taken over all of them (`launch_ms` / `achieved` stay the mean of the K timed
+  # ones); a plain run takes them over its K timed launches.
   all_sorted = launch_sorted
-  if args.steps < PCT_LAUNCHES:
+  if args.full and args.steps < PCT_LAUNCHES:
     all_sorted = sorted(launch_sorted + per_launch_ms(batch.run, PCT_LAUNCHES - args.steps))
 
   extras = {}

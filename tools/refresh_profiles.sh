@@ -12,14 +12,14 @@ cd "$R"
 timeout 600 bash tools/build_kbench.sh > "$OUT/build_kbench.log" 2>&1    # (r05: the probes below were run without having been built)
 timeout 1500 python -m pytest tests -m gpu -q 2>&1 | tail -5 > "$OUT/gpu_tests_tail.txt"
 cp gpurun_out/parity_rates.jsonl "$OUT/" 2>/dev/null
-timeout 600 python bench.py --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
+timeout 600 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench.json" 2> "$OUT/bench.err"
 timeout 400 python tools/path_bench.py --big > "$OUT/path_bench.txt" 2>&1
 trace() {   # name, then the command
   local name=$1; shift
   rm -rf "/tmp/prof_$name"
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace -d "/tmp/prof_$name" -o p -- "$@" > "$OUT/$name.log" 2>&1)
 }
-trace bench python "$R/bench.py" --steps 20 --warmup 5
+trace bench python "$R/bench.py" --full --steps 20 --warmup 5
 python tools/rocprof_summary.py /tmp/prof_bench > "$OUT/bench_kernel_trace.txt" 2>&1
 trace paths python "$R/tools/path_bench.py" --big
 python tools/rocprof_summary.py /tmp/prof_paths > "$OUT/paths_kernel_trace.txt" 2>&1
