@@ -807,3 +807,82 @@ def dwr_max_error(w: torch.Tensor, q: torch.Tensor, scale: torch.Tensor, g: int)
   _ffi.check(_ffi.lib().mi355q_dwr_max_error_f32(rt.ptr(w), rt.ptr(q), rt.ptr(scale), w.numel(), g,
                                                  rt.ptr(out), rt.stream_ptr()))
   return float(out.item())
+
+
+# ------------------------------------------------------- tensor comparison (model validation) ---
+# (include/mi355q.h, mi355q_compare_pair / mi355q_compare_result)
+COMPARE_KINDS = {"f32": 0, "f16": 1, "bf16": 2, "i8": 3, "i16": 4, "i32": 5, "i4": 6, "i2": 7}
+COMPARE_PAIR_DTYPE = np.dtype([("reference", "<u8"), ("target", "<u8"), ("n", "<i8"), ("kind", "<i4"),
+                               ("diff_bits", "<i4"), ("channels", "<i8"), ("inner", "<i8"), ("scale", "<u8"),
+                               ("zero_point", "<u8")])
+COMPARE_RESULT_DTYPE = np.dtype([("sum_sq_diff", "<f4"), ("sum_ref_sq", "<f4"), ("sum_kl", "<f4"),
+                                 ("median_lo", "<f4"), ("median_hi", "<f4"), ("reserved", "<f4"),
+                                 ("dot_tr", "<f8"), ("dot_tt", "<f8"), ("dot_rr", "<f8")])
+COMPARE_MEDIAN = 1
+COMPARE_NO_KL = 2
+
+
+class CompareTarget:
+  """The target operand of a comparison in its stored form, on the device.
+
+  `data`: float32 / float16 / bfloat16 / int8 / int16 / int32 tensor, or uint8 packed bytes with
+  `packed_bits` 4 or 2. Integer targets carry `scale` (float32, `channels` entries) and optional `zero_point`
+  (int32); element e uses entry (e // inner) % channels. `diff_bits` is the width in which q - zp is formed.
+  """
+
+  def __init__(self, data: torch.Tensor, n: int, kind: str, scale: torch.Tensor | None = None,
+               zero_point: torch.Tensor | None = None, channels: int = 1, inner: int = 1, diff_bits: int = 32):
+    if kind not in COMPARE_KINDS:
+      raise ValueError(f"unknown target kind {kind!r}")
+    if COMPARE_KINDS[kind] >= COMPARE_KINDS["i8"] and scale is None:
+      raise ValueError("integer targets need scales")
+    self.data, self.n, self.kind = data.contiguous(), int(n), kind
+    self.scale = None if scale is None else _f32(scale)
+    self.zero_point = None if zero_point is None else zero_point.to(torch.int32).contiguous()
+    self.channels, self.inner, self.diff_bits = int(channels), int(inner), int(diff_bits)
+
+
+def _pair_record(rec, reference: torch.Tensor, target: CompareTarget) -> None:
+  rec["reference"], rec["target"], rec["n"] = reference.data_ptr(), target.data.data_ptr(), target.n
+  rec["kind"], rec["diff_bits"] = COMPARE_KINDS[target.kind], target.diff_bits
+  rec["channels"], rec["inner"] = target.channels, target.inner
+  rec["scale"] = 0 if target.scale is None else target.scale.data_ptr()
+  rec["zero_point"] = 0 if target.zero_point is None else target.zero_point.data_ptr()
+
+
+def compare(pairs, median: bool = True, kl: bool = True) -> np.ndarray:
+  """Comparison sums of (float32 reference, CompareTarget) pairs -> COMPARE_RESULT_DTYPE records (host).
+
+  One pair goes through mi355q_compare_f32 (its descriptor in the kernel arguments), several through one
+  mi355q_compare_f32_batched launch set. Synchronizes (the records are copied to the host).
+  """
+  rt.require_gpu()
+  L = _ffi.lib()
+  pairs = [(_f32(r).view(-1), t) for r, t in pairs]
+  for r, t in pairs:
+    if r.numel() != t.n:
+      raise ValueError("data1 & data2 must be of the same size")
+  out = np.zeros(len(pairs), COMPARE_RESULT_DTYPE)
+  live = [(r, t) for r, t in pairs if t.n > 0]
+  if not live:
+    return out
+  flags = (COMPARE_MEDIAN if median else 0) | (0 if kl else COMPARE_NO_KL)
+  res = rt.empty((len(live) * COMPARE_RESULT_DTYPE.itemsize,), torch.uint8)
+  chunks = sum(L.mi355q_compare_chunks(t.n) for _, t in live)
+  nbytes = L.mi355q_compare_workspace_bytes(len(live), chunks)
+  ws = rt.empty((max(nbytes, 1),), torch.uint8)
+  if len(live) == 1:
+    r, t = live[0]
+    _ffi.check(L.mi355q_compare_f32(
+        rt.ptr(r), rt.ptr(t.data), t.n, COMPARE_KINDS[t.kind], t.diff_bits, t.channels, t.inner, rt.ptr(t.scale),
+        rt.ptr(t.zero_point), flags, rt.ptr(res), rt.ptr(ws), nbytes, rt.stream_ptr()))
+  else:
+    table = np.zeros(len(live), COMPARE_PAIR_DTYPE)
+    for i, (r, t) in enumerate(live):
+      _pair_record(table[i], r, t)
+    dev_table = torch.from_numpy(table.view(np.uint8).copy()).to(rt.device())
+    _ffi.check(L.mi355q_compare_f32_batched(rt.ptr(dev_table), len(live), chunks, flags, rt.ptr(res), rt.ptr(ws),
+                                            nbytes, rt.stream_ptr()))
+  host = res.cpu().numpy().view(COMPARE_RESULT_DTYPE)     # (synchronizes: every operand above is still alive)
+  out[[i for i, (_, t) in enumerate(pairs) if t.n > 0]] = host
+  return out

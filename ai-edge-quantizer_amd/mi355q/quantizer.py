@@ -2,9 +2,10 @@
 
 Covers the weight-requantization flow of the hot path: read the model (zero-copy views of the
 mmap'd file), load a recipe, generate parameters through the registry (GPU kernels), apply the
-QUANTIZE_TENSOR transformation (pack + store + metadata) and serialize. Calibration by running
-the float model (LiteRT interpreter) and model validation are outside this build's scope;
-calibration results (QSVs) are passed in.
+QUANTIZE_TENSOR transformation (pack + store + metadata) and serialize. Running a model (the LiteRT
+interpreter) is outside this build's scope: calibration results (QSVs) are passed in, and `validate()`
+compares the constant tensors on the GPU and takes inputs, outputs and intermediates from a
+caller-supplied `run_signature`.
 """
 from __future__ import annotations
 
@@ -19,16 +20,19 @@ from . import algorithm_manager
 from . import calibrator
 from . import default_policy
 from . import model_modifier
+from . import model_validator
 from . import params_generator
 from . import qtyping
 from . import recipe_manager
 from . import requant_queue
 from .utils import tfl_flatbuffer_utils
 from .utils import tflite_flatbuffer
+from .utils import validation_utils
 
 apply_quantize_tensor_transformations = model_modifier.apply_quantize_tensor_transformations
 
 Path = Union[str, pathlib.Path]
+ValidationErrorMetric = validation_utils.ValidationErrorMetric
 
 
 class _Flag(int):
@@ -68,8 +72,10 @@ class Quantizer:
 
   def __init__(self, float_model: Any,
                quantization_recipe: Optional[Union[Path, qtyping.ModelQuantizationRecipe]] = None):
+    self._model_name: Optional[str] = None     # the float model's path, when it came from one (validate's file names)
     if isinstance(float_model, (str, pathlib.Path)):
       self._float_model_buffer = tfl_flatbuffer_utils.get_model_content(float_model)
+      self._model_name = str(float_model)
       self.float_model = tfl_flatbuffer_utils.read_model(self._float_model_buffer)
     elif isinstance(float_model, (bytes, bytearray, memoryview)):
       self._float_model_buffer = memoryview(float_model)
@@ -174,3 +180,30 @@ class Quantizer:
     self.quantized_model_object = modifier.quantized_model_object
     self._result = QuantizationResult(self.get_quantization_recipe(), serialized)
     return self._result
+
+  def validate(self, test_data=None, error_metrics=None, use_xnnpack: bool = True, num_threads: int = 16,
+               validate_output_tensors_only: bool = False, save_folder: Optional[str] = None,
+               model_name: Optional[str] = None, *, run_signature=None) -> model_validator.ComparisonResult:
+    """Numerical validation of the last quantize() result against the float model (ref :507-576).
+
+    Constant tensors are compared on the GPU straight from the two flatbuffers. Input, output and intermediate
+    tensors need a run of both models: `run_signature(model_bytes, signature_key, inputs) -> {tensor name: array}`
+    is the caller's interpreter (without it only the constants are filled; with it and no `test_data`, one seeded
+    random sample per signature is used). `use_xnnpack` and `num_threads` are accepted and ignored.
+    """
+    quantized_model = self._result.quantized_model
+    if quantized_model is None:
+      raise ValueError("No quantized model available to validate.")
+    if self._float_model_buffer is not None:
+      float_model = self._float_model_buffer    # (a mapped file stays mapped: see model_validator.compare_model)
+    else:
+      float_model = bytes(tflite_flatbuffer.write_model(self.float_model))
+    results = model_validator.compare_model(
+        float_model, bytes(quantized_model), test_data, error_metrics, compare_fns=None,
+        use_xnnpack=use_xnnpack, num_threads=num_threads,
+        validate_output_tensors_only=validate_output_tensors_only, run_signature=run_signature)
+    if save_folder:
+      if model_name is None:
+        model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"
+      results.save(save_folder, model_name=model_name)
+    return results

@@ -620,6 +620,77 @@ int32_t mi355q_file_io_submit_download(const void* src, int64_t nbytes, int32_t 
 int32_t mi355q_file_io_submit_download_mapped(const void* src, int64_t nbytes, void* dst, void* copy_stream,
                                               void* ready_event);
 
+/* ------------------------------------------------------------------------
+ * Tensor comparison for model validation: the five metrics of the reference's
+ * validation_utils for one float32 REFERENCE operand against a TARGET read in
+ * its stored form (dequantized in registers, never written back as float32).
+ * ref: utils/validation_utils.py:63-255, model_validator.py:357-361
+ *
+ * Both operands go through np.nan_to_num(nan=1e-9, neginf=-1e9, posinf=1e9).
+ * Integer targets are viewed as [outer, channels, inner]: element e uses
+ * scale[c] / zero_point[c] with c = (e / inner) % channels (channels = 1:
+ * per tensor; blockwise along the last axis: channels = n / block, inner =
+ * block). (q - zp) is formed in a `diff_bits`-wide integer and wraps, as NumPy
+ * does in the promoted type of (q, zero_point); diff_bits 32 multiplies in
+ * float64 and casts to float32, 8 / 16 multiply in float32
+ * (ref: uniform_quantize_tensor.py:365-409). I4 / I2 are packed as pack_bits
+ * writes them, element 0 in the low bits.
+ *
+ * Per pair the result carries
+ *   sum_sq_diff  Sum (t - r)^2        float32, NumPy's order for np.sum of a
+ *   sum_ref_sq   Sum r^2              contiguous 1-D array (8192-element
+ *   sum_kl       Sum p log((p+e)/(q+e)), p = max(0, r), q = max(0, t), e = 1e-9
+ *                                     chunks, pairwise inside, added in order)
+ *   median_lo/hi the lower / upper middle value of |t - r| / (|r| + 1e-6)
+ *                (equal for odd n); only with MI355Q_COMPARE_MEDIAN
+ *   dot_tr/tt/rr float32 products summed in float64 (cosine similarity).
+ * The means and ratios are formed on the host. n = 0 enqueues nothing.
+ * workspace: mi355q_compare_workspace_bytes(count, total_chunks), where
+ * total_chunks = Sum mi355q_compare_chunks(n_i) (count = 1 for the single form).
+ * ------------------------------------------------------------------------ */
+enum {
+  MI355Q_CMP_F32 = 0,
+  MI355Q_CMP_F16 = 1,
+  MI355Q_CMP_BF16 = 2,
+  MI355Q_CMP_I8 = 3,
+  MI355Q_CMP_I16 = 4,
+  MI355Q_CMP_I32 = 5,
+  MI355Q_CMP_I4 = 6,
+  MI355Q_CMP_I2 = 7
+};
+#define MI355Q_COMPARE_MEDIAN 1   /* median_lo / median_hi (three more passes over the operands) */
+#define MI355Q_COMPARE_NO_KL 2    /* skip sum_kl (left 0): no logf per element */
+
+typedef struct mi355q_compare_pair {
+  const float* reference;      /* n float32 */
+  const void* target;          /* n elements of target_kind (packed for I4 / I2) */
+  int64_t n;
+  int32_t target_kind;         /* MI355Q_CMP_* */
+  int32_t diff_bits;           /* integer kinds: 8, 16 or 32 */
+  int64_t channels, inner;     /* integer kinds: the scale view */
+  const float* scale;          /* integer kinds: `channels` entries */
+  const int32_t* zero_point;   /* integer kinds: `channels` entries, or NULL (all zero) */
+} mi355q_compare_pair;         /* 64 bytes */
+
+typedef struct mi355q_compare_result {
+  float sum_sq_diff, sum_ref_sq, sum_kl;
+  float median_lo, median_hi, reserved;
+  double dot_tr, dot_tt, dot_rr;
+} mi355q_compare_result;       /* 48 bytes */
+
+int64_t mi355q_compare_chunks(int64_t n);
+size_t mi355q_compare_workspace_bytes(int32_t count, int64_t total_chunks);
+int32_t mi355q_compare_f32(const float* reference, const void* target, int64_t n, int32_t target_kind,
+                           int32_t diff_bits, int64_t channels, int64_t inner, const float* scale,
+                           const int32_t* zero_point, int32_t flags, mi355q_compare_result* result,
+                           void* workspace, size_t workspace_bytes, void* stream);
+/* `count` pairs in one set of launches; `pairs` is a DEVICE table, so its entries are checked on the device: when
+ * an entry is invalid (as mi355q_compare_f32 would refuse it) or total_chunks is not Sum mi355q_compare_chunks(n_i),
+ * no operand is read and every result of the call is NaN. */
+int32_t mi355q_compare_f32_batched(const mi355q_compare_pair* pairs, int32_t count, int64_t total_chunks,
+                                   int32_t flags, mi355q_compare_result* results, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
