@@ -705,8 +705,11 @@ __global__ __launch_bounds__(256) void clip_scan_wave_kernel(
 //      B = 64 g 2^-53 (a_1^2 noise + 4 S_a2m(g)) of its exact value (g positive addends per sum, a handful of
 //      roundings in the closed form, every intermediate <= the bracket; S_a2m(g) <= S_a2m(P) + a_next^2 M), so
 //      E(a_next) computed > best + 4 B implies that every later computed candidate exceeds the best of the prefix:
-//      np.argmin's first minimum is the prefix's. Otherwise -- or when a key is not finite, or more than `cap`
-//      elements share the top eighths -- the row is flagged and the full sort + scan answers it (todo[row] = 1).
+//      np.argmin's first minimum is the prefix's. M = sum(m) + 1e-12 is summed from the caller's masses on the device
+//      (mass_total_kernel), not read off noise: u and noise are whatever the caller passes (u only places the
+//      candidates inside their intervals; E needs noise >= 0 and m >= 0 to be convex, checked). Otherwise -- or when
+//      a key is not finite, or more than `cap` elements share the top eighths -- the row is flagged and the full sort +
+//      scan answers it (todo[row] = 1).
 // Rows of up to 4096 columns are ONE WAVE's work (WAVES = 1: 16 / 32 / 64 elements per lane): no workgroup barrier
 // anywhere, twenty rows in flight per CU. The first form of this kernel gave every row a 256-thread workgroup: 110 000
 // cycles per row, half of them in the 45 barriers of the sort with six workgroups per CU taking turns
@@ -714,10 +717,40 @@ __global__ __launch_bounds__(256) void clip_scan_wave_kernel(
 // waves with 16 each left a CU one row at a time: 433 us for 2048 x 16384).
 // Ref oscar.py:62-104. The answer is the reference's, bit for bit, on either route.
 
+// M = sum(m) + 1e-12 of the row's d masses, the mass bound of step 4 (in any order: a relative error of d 2^-53 is far
+// inside the bound's margin). A negative or NaN mass makes it NaN, which keeps every row off the prefix route.
+// One workgroup, eight loads in flight per thread: 16384 masses are two load round trips (a loop of one load per trip
+// cost 12 us in front of the prefix kernel of 2048 x 16384).
+__global__ __launch_bounds__(1024) void mass_total_kernel(const double* __restrict__ m, int64_t d, double* __restrict__ out) {
+  constexpr int B = 8;
+  double acc = 0.0;
+  for (int64_t j0 = threadIdx.x; j0 < d; j0 += 1024 * B) {
+    double v[B];
+#pragma unroll
+    for (int b = 0; b < B; ++b) v[b] = j0 + 1024 * b < d ? m[j0 + 1024 * b] : 0.0;
+#pragma unroll
+    for (int b = 0; b < B; ++b) acc = acc + (v[b] >= 0.0 ? v[b] : __builtin_nan(""));
+  }
+#pragma unroll
+  for (int off = 1; off < kWave; off <<= 1) acc = acc + __shfl_xor(acc, off, kWave);
+  __shared__ double part[16];
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double total = 0.0;
+    for (int k = 0; k < 16; ++k) total = total + part[k];
+    out[0] = total + 1e-12;
+  }
+}
+
 // (float32 pattern of a key, monotone in the key for finite keys >= 0; anything else -- NaN, inf, a negative product --
-// maps to 0x7F800000 or above and sends the row to the full route)
+// maps to 0x7F800000 or above and sends the row to the full route. A positive key below 2^-133 -- its float32 pattern's
+// upper half is 0 -- is raised to the smallest non-zero upper half: only exact zeros may look like zeros, else a row
+// whose other elements are all such keys would take a_next = 0 for a positive next key)
 __device__ __forceinline__ uint32_t key_bits(float w, double s) {
-  return f2u(static_cast<float>(fabs(static_cast<double>(w)) * s));
+  const double key = fabs(static_cast<double>(w)) * s;
+  const uint32_t b = f2u(static_cast<float>(key));
+  return (b < 0x10000u && key > 0.0) ? 0x10000u : b;
 }
 
 __device__ __forceinline__ uint64_t key_composite(double key, uint32_t position) {
@@ -764,7 +797,8 @@ template <int EPT, int WAVES>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 4 : 1) void clip_prefix_kernel(      // (one-wave form: four waves per SIMD, 128 VGPRs)
     const float* __restrict__ w, const double* __restrict__ s, const double* __restrict__ m, int64_t n,
     int32_t g, int32_t target, const double* __restrict__ u, const double* __restrict__ noise, double qmax,
-    int32_t blockwise, double* __restrict__ bounds, double* __restrict__ scale, uint8_t* __restrict__ todo) {
+    const double* __restrict__ mass_total, int32_t blockwise, double* __restrict__ bounds, double* __restrict__ scale,
+    uint8_t* __restrict__ todo) {
   constexpr int THREADS = 64 * WAVES;
   constexpr int CAP = WAVES == 1 ? 512 : 1024;
   __shared__ uint64_t comp[CAP + CAP / 8 + CAP / 32 + 2];
@@ -910,10 +944,15 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 4 : 1) void clip_prefix_ke
   uint16_t* next_pos = sel_pos + CAP;
   static_assert(sizeof(stage) >= 2 * (CAP + kNextCap), "position lists");
   uint32_t listed = 0;
+  if constexpr (WAVES > 1) {
+    // the counter now counts the listed elements, and only them: every wave has its stretch of the selected list (its
+    // atomic returned before the barrier of the reduction above), and a row without a next element (below == 0: the
+    // unselected elements are all zero) lists nothing -- n_next = filled below is 0 then, never the selected count
+    if (tid == 0) filled = 0;
+    __syncthreads();
+  }
   if (below != 0u) {
     if constexpr (WAVES > 1) {
-      if (tid == 0) filled = 0;                      // (every wave has its stretch of the selected list: the counter is free)
-      __syncthreads();
       uint32_t mine = 0;
 #pragma unroll
       for (int k = 0; k < EPT; ++k) mine += static_cast<uint32_t>(__builtin_popcountll(__ballot(pattern(k) == below)));
@@ -929,7 +968,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 4 : 1) void clip_prefix_ke
       listed += static_cast<uint32_t>(__builtin_popcountll(mask));
     }
   }
-  uint32_t n_next = listed;                          // WAVES == 1: the count; WAVES > 1: read back below
+  uint32_t n_next = listed;                          // WAVES == 1: the count; WAVES > 1: read back below (0 when below == 0)
   if constexpr (WAVES > 1) {
     __syncthreads();
     n_next = filled;
@@ -1102,14 +1141,16 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 1 ? 4 : 1) void clip_prefix_ke
   const double s_m = __shfl(acc, 0, kWave), s_am = __shfl(acc, 1, kWave), s_a2m = __shfl(acc, 2, kWave);
   bool done = Pn == g;
   if (!done) {
-    const double mass = (12.0 * qmax * qmax) * nk;                        // M (+ 1e-12), as the host formed noise from it
+    const double mass = mass_total[0];                                    // sum(m) + 1e-12 of the caller's masses (mass_total_kernel)
     const double t_max = (a0 * a0) * nk + 4.0 * (s_a2m + (a_next * a_next) * mass);
     const double slack = 64.0 * static_cast<double>(g) * 1.1102230246251565e-16 * t_max;
     const double stationary = (2.0 * s_am) / (uk + 2.0 * s_m);
     const double an2 = a_next * a_next;
     const double e_next = ((an2 * nk + s_a2m) - (2.0 * a_next) * s_am) + an2 * s_m;
-    // (every comparison is false when one of its operands is NaN, and inf fails `t_max < inf`)
-    done = stationary >= a_next * (1.0 + 1e-6) && e_next > best_e + 4.0 * slack && t_max < __builtin_inf() && best_e >= 0.0;
+    // (every comparison is false when one of its operands is NaN, and inf fails `t_max < inf`; E is convex only for
+    // noise >= 0 -- and masses >= 0, else `mass` is NaN)
+    done = stationary >= a_next * (1.0 + 1e-6) && e_next > best_e + 4.0 * slack && t_max < __builtin_inf() && best_e >= 0.0 &&
+           nk >= 0.0;
   }
   if (__ballot(out_of_order) != 0) done = false;
   if (lane == 0) {
@@ -1303,8 +1344,8 @@ extern "C" int32_t mi355q_oscar_clip_workspace_bytes(int64_t n, int64_t d, int64
   const int64_t total = n * d;
   if (total > 0xFFFFFFFFll - g) return fail(MI355Q_UNSUPPORTED, "oscar clip: more than 2^32 weights");
   // two (key, value) slabs: the run merges ping-pong between them; behind them one byte per segment (the rows the prefix
-  // kernel left to the full sort, clip_prefix_kernel)
-  *bytes_out = 4 * align256(static_cast<size_t>(total) * sizeof(double)) + align256(static_cast<size_t>(total / g));
+  // kernel left to the full sort, clip_prefix_kernel) and the total of the masses (mass_total_kernel)
+  *bytes_out = 4 * align256(static_cast<size_t>(total) * sizeof(double)) + align256(static_cast<size_t>(total / g)) + 256;
   return MI355Q_OK;
 }
 
@@ -1411,6 +1452,9 @@ extern "C" int32_t mi355q_oscar_clip_bounds_f32(const float* w, const double* s,
 #endif
   if (prefix_on && g == d && n > 0 && g >= MI355Q_OSCAR_PREFIX_MIN && g <= 16384 && qmax >= 7) {
     uint8_t* flags = static_cast<uint8_t*>(workspace) + 4 * align256(static_cast<size_t>(total) * sizeof(double));
+    double* mass_total = reinterpret_cast<double*>(flags + align256(static_cast<size_t>(segments)));
+    hipLaunchKernelGGL(mass_total_kernel, dim3(1), dim3(1024), 0, st, m, d, mass_total);
+    MI355Q_CHECK_LAUNCH("oscar_mass_total");
     // elements asked for: a sixteenth of the row within [128, 256] for the one-wave form (it sorts at most 512), a
     // thirty-second within [256, 512] beyond (at most 1024 sorted)
     int64_t target = g / 16;
@@ -1423,7 +1467,7 @@ extern "C" int32_t mi355q_oscar_clip_bounds_f32(const float* w, const double* s,
 #define MI355Q_LAUNCH_PREFIX(EPT, WAVES)                                                                                \
   hipLaunchKernelGGL((clip_prefix_kernel<EPT, WAVES>), dim3(static_cast<unsigned>(n)), dim3(64 * WAVES), 0, st, w, s, m, n, \
                      static_cast<int32_t>(g), static_cast<int32_t>(target), u, noise, static_cast<double>(qmax),       \
-                     blockwise_scale, bounds_out, scale_out, flags)
+                     mass_total, blockwise_scale, bounds_out, scale_out, flags)
     if (g <= 1024) MI355Q_LAUNCH_PREFIX(16, 1);
     else if (g <= 2048) MI355Q_LAUNCH_PREFIX(32, 1);
     else if (g <= 4096) MI355Q_LAUNCH_PREFIX(64, 1);

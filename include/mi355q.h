@@ -471,17 +471,19 @@ int32_t mi355q_oscar_winner_energy_f64(const int32_t* winner, const double* wsq,
 /* Optimal clip bound of every segment of g consecutive elements of the flattened [n, d]
  * matrix (g divides d, or g == n*d for TENSORWISE): stable descending sort of |w|*s carrying
  * the masses m[j], sequential running sums, closed-form candidate per breakpoint interval,
- * first minimum (ref oscar.py:62-108). u[k] = M_k/(6 qmax^2), noise[k] = M_k/(12 qmax^2) with
- * M_k the group's total mass + 1e-12, k = column group (host FP64).
+ * first minimum (ref oscar.py:62-108). u[k], noise[k] per column group k (host FP64); the product passes
+ * u[k] = M_k/(6 qmax^2), noise[k] = M_k/(12 qmax^2) with M_k the group's total mass + 1e-12, but any
+ * values are accepted and used as given.
  * scale_out (optional) is tensor_zp_scale_from_min_max(-bound, bound) of the symmetric signed
  * target: max(bound, 1e-9) / qmax, and with blockwise_scale != 0 rounded FP64 -> float32 ->
  * bfloat16 -> float16 (ref uniform_quantize_tensor.py:553-581), stored as double.
  *   bounds_out / scale_out double [n*d/g], either may be NULL;
  *   workspace: mi355q_oscar_clip_workspace_bytes(n, d, g) (two (key, mass) slabs for the sort's merge passes + one byte per
- *   segment).
- * CHANNELWISE rows (g == d, 1024 <= g <= 16384, qmax >= 7) are answered from a sorted prefix of their largest magnitudes
+ *   segment + the masses' total).
+ * CHANNELWISE rows (g == d, 384 <= g <= 16384, qmax >= 7) are answered from a sorted prefix of their largest magnitudes
  * where a convexity argument with an explicit rounding bound shows that no later breakpoint can hold the first minimum;
- * rows where it cannot take the full sort + scan. Same bits either way (csrc/oscar.hip: clip_prefix_kernel).
+ * rows where it cannot take the full sort + scan. Same bits either way, for any u / noise: the bound takes the total
+ * mass from m itself, and rows with noise < 0 or a negative mass take the full route (csrc/oscar.hip: clip_prefix_kernel).
  * Environment: MI355Q_OSCAR_PREFIX=0 full sort + scan for every row; MI355Q_OSCAR_PREFIX_TARGET=<n> elements asked for. */
 int32_t mi355q_oscar_clip_workspace_bytes(int64_t n, int64_t d, int64_t g, size_t* bytes_out);
 int32_t mi355q_oscar_clip_bounds_f32(const float* w, const double* s, const double* m, int64_t n,
