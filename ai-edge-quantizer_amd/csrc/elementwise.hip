@@ -208,18 +208,19 @@ MinMaxPlan plan_minmax(int64_t outer, int64_t channels, int64_t inner) {
 }
 
 // ------------------------------------------------------------------ K3 ---
+// NumPy's float -> int cast on x86: cvttss2si / cvttsd2si give the "integer indefinite" INT_MIN for NaN and for values
+// out of the int32 range; int8 / int16 take the low bits of that, 0 (np.float32('nan').astype(np.int32) == INT_MIN).
 template <typename OutT>
 __device__ __forceinline__ OutT sat_cast(float r, bool isnan_) {
-  if (isnan_) return 0;
+  if (isnan_) return sizeof(OutT) == 4 ? static_cast<OutT>(INT_MIN) : static_cast<OutT>(0);
   if constexpr (sizeof(OutT) == 4) {
-    // x86 cvttss2si "integer indefinite" for out-of-range values
     if (!(r < 2147483648.0f) || r < -2147483648.0f) return INT_MIN;
   }
   return static_cast<OutT>(r);
 }
 template <typename OutT>
 __device__ __forceinline__ OutT sat_cast(double r, bool isnan_) {
-  if (isnan_) return 0;
+  if (isnan_) return sizeof(OutT) == 4 ? static_cast<OutT>(INT_MIN) : static_cast<OutT>(0);
   if constexpr (sizeof(OutT) == 4) {
     if (!(r < 2147483648.0) || r < -2147483648.0) return INT_MIN;
   }
@@ -380,20 +381,22 @@ __global__ __launch_bounds__(256) void dequantize_rows_vec4_kernel(
   }
 }
 
-template <typename InT, typename OutT>
+template <typename InT, typename OutT, typename ScaleT>
 __global__ __launch_bounds__(256) void dequantize_kernel(
     const InT* __restrict__ q, int64_t n, int64_t channels, int64_t inner,
-    const float* __restrict__ scale, const int32_t* __restrict__ zp, int diff_bits,
+    const ScaleT* __restrict__ scale, const int32_t* __restrict__ zp, int diff_bits,
     OutT* __restrict__ out) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * 256;
   for (int64_t e = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x; e < n; e += stride) {
     const int64_t c = channels == 1 ? 0 : (e / inner) % channels;
     const int z = zp ? zp[c] : 0;
     // NumPy subtracts in the promoted integer type of (q, zero_point) and wraps:
-    // int8 - int8 stays int8 (ref: uniform_quantize_tensor.py:407-409).
-    int d = static_cast<int>(q[e]) - z;
+    // int8 - int8 stays int8, int32 - int32 wraps at 32 bits, int32 - int64 does not wrap
+    // (ref: uniform_quantize_tensor.py:407-409).
+    int64_t d = static_cast<int64_t>(q[e]) - z;
     if (diff_bits == 8) d = static_cast<int8_t>(d);
     else if (diff_bits == 16) d = static_cast<int16_t>(d);
+    else if (diff_bits == 32) d = static_cast<int32_t>(d);
     out[e] = static_cast<OutT>(d) * static_cast<OutT>(scale[c]);
   }
 }
@@ -747,37 +750,45 @@ extern "C" int32_t mi355q_quantize_f32(const float* x, int64_t outer, int64_t ch
 }
 
 extern "C" int32_t mi355q_dequantize_f32(const void* q, int32_t in_bits, int64_t outer,
-                                         int64_t channels, int64_t inner, const float* scale,
-                                         const int32_t* zero_point, int32_t diff_bits,
-                                         int32_t out_is_f64, void* out, void* stream) {
+                                         int64_t channels, int64_t inner, const void* scale,
+                                         int32_t scale_is_f64, const int32_t* zero_point,
+                                         int32_t diff_bits, int32_t out_is_f64, void* out,
+                                         void* stream) {
   clear_error();
   if (outer < 0 || channels < 0 || inner < 0) return fail(MI355Q_BAD_ARG, "negative shape");
   const int64_t n = outer * channels * inner;
   if (n == 0) return MI355Q_OK;
   if (!q || !scale || !out) return fail(MI355Q_BAD_ARG, "null pointer");
-  if (diff_bits != 8 && diff_bits != 16 && diff_bits != 32)
-    return fail(MI355Q_BAD_ARG, "diff_bits must be 8, 16 or 32");
+  if (diff_bits != 8 && diff_bits != 16 && diff_bits != 32 && diff_bits != 64)
+    return fail(MI355Q_BAD_ARG, "diff_bits must be 8, 16, 32 or 64");
+  if (scale_is_f64 && !out_is_f64)
+    return fail(MI355Q_BAD_ARG, "a float64 scale needs a float64 output (NumPy promotes the product)");
   hipStream_t st = as_stream(stream);
   const dim3 grid(grid_for(n)), blk(256);
-  if (in_bits == 8 && !out_is_f64 && inner % 4 == 0 && inner >= 1024 &&
+  if (in_bits == 8 && !out_is_f64 && !scale_is_f64 && diff_bits <= 32 && inner % 4 == 0 && inner >= 1024 &&
       ((reinterpret_cast<uintptr_t>(q) & 3u) | (reinterpret_cast<uintptr_t>(out) & 15u)) == 0 &&
       (n / inner) * ((inner / 4 + kRowPiece - 1) / kRowPiece) < 0x7FFFFFFFLL) {
     const int64_t inner4 = inner / 4, pieces = (inner4 + kRowPiece - 1) / kRowPiece;
     hipLaunchKernelGGL(dequantize_rows_vec4_kernel, dim3(static_cast<unsigned>((n / inner) * pieces)), blk, 0, st,
-                       static_cast<const uint32_t*>(q), channels, inner4, static_cast<int32_t>(pieces), scale, zero_point,
-                       diff_bits, static_cast<float4*>(out));
+                       static_cast<const uint32_t*>(q), channels, inner4, static_cast<int32_t>(pieces),
+                       static_cast<const float*>(scale), zero_point, diff_bits, static_cast<float4*>(out));
     MI355Q_CHECK_LAUNCH("dequantize launch");
     return MI355Q_OK;
   }
-#define MI355Q_DQ(IN, OUT)                                                                 \
-  hipLaunchKernelGGL((dequantize_kernel<IN, OUT>), grid, blk, 0, st, static_cast<const IN*>(q), n, \
-                     channels, inner, scale, zero_point, diff_bits, static_cast<OUT*>(out))
+#define MI355Q_DQ(IN, OUT, SC)                                                                     \
+  hipLaunchKernelGGL((dequantize_kernel<IN, OUT, SC>), grid, blk, 0, st, static_cast<const IN*>(q), n, \
+                     channels, inner, static_cast<const SC*>(scale), zero_point, diff_bits, static_cast<OUT*>(out))
+#define MI355Q_DQ_OUT(IN)                                  \
+  if (scale_is_f64) MI355Q_DQ(IN, double, double);         \
+  else if (out_is_f64) MI355Q_DQ(IN, double, float);       \
+  else MI355Q_DQ(IN, float, float)
   switch (in_bits) {
-    case 8: if (out_is_f64) MI355Q_DQ(int8_t, double); else MI355Q_DQ(int8_t, float); break;
-    case 16: if (out_is_f64) MI355Q_DQ(int16_t, double); else MI355Q_DQ(int16_t, float); break;
-    case 32: if (out_is_f64) MI355Q_DQ(int32_t, double); else MI355Q_DQ(int32_t, float); break;
+    case 8: MI355Q_DQ_OUT(int8_t); break;
+    case 16: MI355Q_DQ_OUT(int16_t); break;
+    case 32: MI355Q_DQ_OUT(int32_t); break;
     default: return fail(MI355Q_UNSUPPORTED, "in_bits must be 8, 16 or 32");
   }
+#undef MI355Q_DQ_OUT
 #undef MI355Q_DQ
   MI355Q_CHECK_LAUNCH("dequantize launch");
   return MI355Q_OK;

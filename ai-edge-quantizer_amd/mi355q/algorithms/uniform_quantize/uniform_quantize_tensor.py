@@ -303,18 +303,21 @@ def uniform_dequantize(tensor_data: np.ndarray,
     p = fix_quantization_params_rank(tensor_data, p)
     _is_valid_quantization_params(tensor_data, p)
     scale, zp = p.scale, p.zero_point
+  # the width NumPy subtracts in is that of the data as given (int64 data held in int32 below still
+  # subtracts in 64 bits); the kernel wraps the difference to it
+  diff = np.result_type(tensor_data.dtype, zp.dtype)
   if tensor_data.dtype not in (np.int8, np.int16, np.int32):
     if np.issubdtype(tensor_data.dtype, np.integer) and np.abs(tensor_data).max(initial=0) < 2**31:
       tensor_data = tensor_data.astype(np.int32)
-      zp = zp.astype(np.int32) if zp.dtype.itemsize < 4 else zp
     else:
       raise TypeError(f"uniform_dequantize expects int8/int16/int32 data, got {tensor_data.dtype}")
-  diff = np.result_type(tensor_data.dtype, zp.dtype)
-  diff_bits = min(32, diff.itemsize * 8)
+  diff_bits = min(64, diff.itemsize * 8)
+  if zp.size and (zp.min() < -2**31 or zp.max() >= 2**31):
+    raise ValueError("uniform_dequantize takes zero points in the int32 range")
   if view is None:
     scale, zp = _adjacent_params(tensor_data.shape, scale, zp)
   outer, ch, inner = view or _channel_view(tensor_data.shape, scale.shape)
-  s, z = _flat_params(scale, zp, False)
+  s, z = _flat_params(scale, zp, scale.dtype == np.float64)
   rt.require_gpu()
   out = ops.dequantize(rt.to_device(tensor_data), outer, ch, inner, rt.to_device(s),
                        rt.to_device(z), diff_bits)

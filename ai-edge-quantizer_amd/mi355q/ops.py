@@ -153,16 +153,22 @@ def quantize(x: torch.Tensor, outer: int, channels: int, inner: int, scale: torc
 
 def dequantize(q: torch.Tensor, outer: int, channels: int, inner: int, scale: torch.Tensor,
                zero_point: torch.Tensor | None, diff_bits: int) -> torch.Tensor:
-  """(q - zp) * scale. ref: uniform_quantize_tensor.py:365-409."""
+  """(q - zp) * scale. scale is float32 or float64 [channels]; diff_bits the width of NumPy's
+  promoted (q, zero point) type (8 / 16 / 32 / 64). The output has NumPy's result type: float64
+  for a float64 scale or a 32 / 64-bit difference, else float32. ref: uniform_quantize_tensor.py:365-409."""
   rt.require_gpu()
   in_bits = {torch.int8: 8, torch.int16: 16, torch.int32: 32}[q.dtype]
-  out_f64 = in_bits == 32 or diff_bits == 32
+  if scale.dtype not in (torch.float32, torch.float64) or not scale.is_cuda:
+    raise TypeError(f"scale must be a float32 or float64 device tensor, got {scale.dtype} on {scale.device}")
+  scale_f64 = scale.dtype == torch.float64
+  out_f64 = in_bits == 32 or diff_bits >= 32 or scale_f64
   out = rt.empty(tuple(q.shape), torch.float64 if out_f64 else torch.float32)
   if zero_point is not None:
     zero_point = zero_point.to(torch.int32).contiguous()
   _ffi.check(_ffi.lib().mi355q_dequantize_f32(
-      rt.ptr(q.contiguous()), in_bits, outer, channels, inner, rt.ptr(_f32(scale)),
-      rt.ptr(zero_point), diff_bits, 1 if out_f64 else 0, rt.ptr(out), rt.stream_ptr()))
+      rt.ptr(q.contiguous()), in_bits, outer, channels, inner, rt.ptr(scale.contiguous()),
+      1 if scale_f64 else 0, rt.ptr(zero_point), diff_bits, 1 if out_f64 else 0, rt.ptr(out),
+      rt.stream_ptr()))
   return out
 
 

@@ -20,7 +20,8 @@
  *   - weights are row-major FP32, `rows x cols` with `cols` contiguous (LiteRT
  *     FULLY_CONNECTED / EMBEDDING_LOOKUP layout [out, in]);
  *   - integer outputs are bit-exact with the reference (IEEE division, round half
- *     to even, NaN -> 0); see DESIGN.md for the parity contract.
+ *     to even, NaN -> 0 in 8/16-bit and INT32_MIN in 32-bit containers, as NumPy's
+ *     x86 cast); see DESIGN.md for the parity contract.
  */
 #ifndef MI355Q_H_
 #define MI355Q_H_
@@ -139,7 +140,9 @@ int32_t mi355q_requant_sym_f32_batched_hostptrs(const float* const* x_ptrs_host,
  *   zp_via_f64   : the reference adds an int32/int64 zero point in FP64 and rounds
  *                  back to FP32 (np.add(f32, int32, out=f32)); int8/int16 zero points
  *                  are added in FP32. Pass 1 for the former.
- *   out_bits     : container of q_out: 8 -> int8, 16 -> int16, 32 -> int32
+ *   out_bits     : container of q_out: 8 -> int8, 16 -> int16, 32 -> int32. A NaN quotient
+ *                  casts as NumPy's does on x86: 0 in int8 / int16, INT32_MIN in int32 (as does
+ *                  a value past the int32 range), for either scale type
  * ------------------------------------------------------------------------ */
 int32_t mi355q_quantize_f32(const float* x, int64_t outer, int64_t channels, int64_t inner,
                             const void* scale, int32_t scale_is_f64,
@@ -148,15 +151,18 @@ int32_t mi355q_quantize_f32(const float* x, int64_t outer, int64_t channels, int
 
 /* (q - zp) * scale. ref: uniform_quantize_tensor.py:365-409.
  * q is int8/int16/int32 per in_bits; same [outer, channels, inner] view.
- *   diff_bits  : width NumPy subtracts in = promoted type of (q, zero_point):
- *                8 when both are int8 (the difference wraps, as in the reference),
- *                16 / 32 otherwise
- *   out_is_f64 : 0 -> float32 out (int8/int16 times float32 scale);
- *                1 -> double out (NumPy promotes int32 * float32 to float64) */
+ *   scale_is_f64 : scale points at double[channels] (NumPy multiplies by the float64 scale);
+ *                  needs out_is_f64
+ *   diff_bits    : width NumPy subtracts in = promoted type of (q, zero_point):
+ *                  8 when both are int8 (the difference wraps, as in the reference),
+ *                  16 / 32 (wraps likewise), 64 (an int64 zero point: no wrap)
+ *   out_is_f64   : 0 -> float32 out (int8/int16 times float32 scale);
+ *                  1 -> double out (NumPy promotes int32 / int64 * float32 and anything
+ *                  * float64 to float64) */
 int32_t mi355q_dequantize_f32(const void* q, int32_t in_bits, int64_t outer,
-                              int64_t channels, int64_t inner, const float* scale,
-                              const int32_t* zero_point, int32_t diff_bits,
-                              int32_t out_is_f64, void* out, void* stream);
+                              int64_t channels, int64_t inner, const void* scale,
+                              int32_t scale_is_f64, const int32_t* zero_point,
+                              int32_t diff_bits, int32_t out_is_f64, void* out, void* stream);
 
 /* ------------------------------------------------------------------------
  * float_casting -- float32 weights stored as float16 (round to nearest even, overflow -> inf,

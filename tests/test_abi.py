@@ -57,6 +57,23 @@ def test_argument_validation_without_gpu(lib):
   assert lib.mi355q_act_minmax_workspace_bytes(3) == 3 * 64 * 5 * 4
 
 
+def test_dequantize_scale_and_difference_arguments_without_gpu(lib):
+  # Host buffers stand in for device pointers: every one of these calls returns before it launches.
+  import ctypes
+  buf = ctypes.create_string_buffer(64)
+  p = ctypes.c_void_p(ctypes.addressof(buf))
+  # (q, in_bits, outer, channels, inner, scale, scale_is_f64, zero_point, diff_bits, out_is_f64, out, stream)
+  st = lib.mi355q_dequantize_f32(p, 8, 1, 1, 4, p, 1, None, 8, 0, p, None)
+  assert st == -1 and b"float64 scale needs a float64 output" in lib.mi355q_last_error()
+  for diff_bits in (0, 12, 24, 48, 128):
+    st = lib.mi355q_dequantize_f32(p, 8, 1, 1, 4, p, 0, None, diff_bits, 1, p, None)
+    assert st == -1 and b"diff_bits must be 8, 16, 32 or 64" in lib.mi355q_last_error()
+  st = lib.mi355q_dequantize_f32(p, 8, 1, 1, 4, None, 1, None, 64, 1, p, None)
+  assert st == -1 and b"null pointer" in lib.mi355q_last_error()
+  st = lib.mi355q_dequantize_f32(None, 8, 1, 0, 4, None, 1, None, 64, 1, None, None)
+  assert st == 0   # empty tensor is a no-op
+
+
 def test_product_path_refuses_to_run_without_gpu(lib):
   import torch
   if torch.cuda.is_available():
