@@ -114,6 +114,18 @@ int32_t check_shape(int64_t rows, int64_t cols, int32_t block, int32_t bits,
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// The widest store a vector kernel issues to q (packed: the same scaled by bits / 8): the rows kernels emit one float4
+// at a time (a dword of int8, 16 bits of int4, a byte of int2), the groups kernels two (CL = 2). 1 where launch_bits()
+// takes the generic kernel, which stores bytes. Equally shaped slices of one 16-byte aligned allocation always comply.
+inline unsigned out_align(int64_t cols, int32_t block, int32_t bits, bool packed) {
+  const bool vec = cols % 4 == 0 && (block > 0 ? (block == 32 || block == 64 || block == 128 || block == 256)
+                                               : cols / 4 <= 256 * 16);
+  if (!vec) return 1;
+  const unsigned q = block > 0 ? 4u * kGroupsCL<8> : 4u;
+  const unsigned a = packed ? q * static_cast<unsigned>(bits) / 8u : q;
+  return a < 1 ? 1 : a;
+}
+
 }  // namespace
 }  // namespace mi355q
 
@@ -169,6 +181,11 @@ extern "C" int32_t mi355q_requant_sym_f32_batched_hostptrs(
     // which equally shaped slices of one allocation are whenever cols % 4 == 0 -- the vector kernels' own condition)
     if (!al16(x_ptrs_host[i]))
       return fail(MI355Q_BAD_ARG, "the batched forms take 16-byte aligned inputs (entry %d)", i);
+    const unsigned qa = out_align(cols, block, bits, false), pa = out_align(cols, block, bits, true);
+    if ((q_ptrs_host && reinterpret_cast<uintptr_t>(q_ptrs_host[i]) % qa) ||
+        (packed_ptrs_host && reinterpret_cast<uintptr_t>(packed_ptrs_host[i]) % pa))
+      return fail(MI355Q_BAD_ARG, "output not aligned to the kernel's store width (%u bytes for q, %u for packed; entry %d)",
+                  qa, pa, i);
   }
   for (int32_t first = 0; first < count; first += kInlineTensors) {
     const int n = count - first < kInlineTensors ? count - first : kInlineTensors;

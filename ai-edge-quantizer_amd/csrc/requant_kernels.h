@@ -97,13 +97,19 @@ __device__ __forceinline__ float make_scale(uint32_t absmax_bits, const float* c
       pos = fminf(pos, 65280.0f * static_cast<float>((1 << BITS) - 1));
       neg = fmaxf(neg, -65280.0f * static_cast<float>(1 << BITS));
     }
-    // np.clip(bound, neg, pos) = minimum(maximum(bound, neg), pos), both NaN-propagating:
-    // a NaN bound stays NaN (fminf / fmaxf would return the other operand), a NaN clip makes it NaN
-    if (bound == bound) bound = fminf(fmaxf(bound, neg), pos);
-    if (clip_nan) bound = clip[g];
+    // np.clip(bound, neg, pos) = minimum(maximum(bound, neg), pos), both NaN-propagating and both handing back the
+    // NaN they meet first: a NaN bound stays as it is (fminf / fmaxf would return the other operand), and a NaN clip
+    // reaches a number as `neg`, so the scale carries the sign of -clip (0xFFC00000 for clip = +NaN, as NumPy's does)
+    if (bound == bound) bound = clip_nan ? -clip[g] : fminf(fmaxf(bound, neg), pos);
   }
   float s = bound / QRange<BITS>::qmax;
-  if constexpr (BLOCKWISE) s = round_scale_blockwise(s, half_bits);
+  if constexpr (BLOCKWISE) {
+    s = round_scale_blockwise(s, half_bits);
+    if (s != s) {  // the reference's bfloat16 step hands back the one quiet NaN, whatever sign or payload went in
+      s = u2f(0x7FC00000u);
+      *half_bits = 0x7E00u;
+    }
+  }
   return s;
 }
 
@@ -312,14 +318,18 @@ __global__ __launch_bounds__(256) void requant_rows_kernel(ARGS a) {
 
 // ------------------------------------------------------------------------
 // (C) generic fallback: any cols (also cols % 4 != 0), any group length. One
-// block per group, two sweeps (the second one hits L2). Packed output is not
-// produced here (the host entry refuses ragged packing; use mi355q_pack_bits).
+// block per group, two sweeps (the second one hits L2). Sub-byte packed output is
+// not produced here (the host entry refuses it; use mi355q_pack_bits).
 // ------------------------------------------------------------------------
 template <int BITS, bool BLOCKWISE, bool BATCHED, typename ARGS = RequantArgs>
 __global__ __launch_bounds__(256) void requant_generic_kernel(ARGS a) {
   const int t = BATCHED ? blockIdx.y : 0;
   const float* __restrict__ x = pick<BATCHED, const float>(a.x, t);
   int8_t* q = pick<BATCHED, int8_t>(a.q, t);
+  // 8-bit `packed` is the same bytes as q; sub-byte packing never gets here (launch_bits refuses it)
+  int8_t* q2 = BITS == 8 ? pick<BATCHED, int8_t>(a.packed, t) : nullptr;
+  if (q2 == q) q2 = nullptr;
+  if (q == nullptr) { q = q2; q2 = nullptr; }
   float* scale = pick<BATCHED, float>(a.scale, t);
   uint16_t* scale_f16 = pick<BATCHED, uint16_t>(a.scale_f16, t);
   const float* clip = BATCHED ? nullptr : a.clip;
@@ -342,8 +352,12 @@ __global__ __launch_bounds__(256) void requant_generic_kernel(ARGS a) {
   }
   if (q != nullptr) {
     int8_t* qg = q + g * glen;
-    for (int64_t i = threadIdx.x; i < glen; i += 256)
-      qg[i] = static_cast<int8_t>(quant_sym<BITS>(xg[i], s));
+    int8_t* qg2 = q2 != nullptr ? q2 + g * glen : nullptr;
+    for (int64_t i = threadIdx.x; i < glen; i += 256) {
+      const int8_t v = static_cast<int8_t>(quant_sym<BITS>(xg[i], s));
+      qg[i] = v;
+      if (qg2 != nullptr) qg2[i] = v;
+    }
   }
 }
 

@@ -94,8 +94,14 @@ int32_t mi355q_minmax_f32(const float* x, int64_t outer, int64_t channels, int64
  *   scale_out  : float[n_scales] (required)
  *   scale_f16_out : NULL, or uint16[n_scales] IEEE half bit patterns of
  *                f16(bf16(scale)) -- what transformations/quantize_tensor.py:129-137
- *                stores in the `<name>_scales` tensor
+ *                stores in the `<name>_scales` tensor. Blockwise only: with block == 0 the
+ *                reference rounds no scale and nothing is written here
  * One HBM read of x; scales, q and packed bytes are written once.
+ * x, q_out and packed_out 16-byte aligned with cols % 4 == 0, cols <= 16384 (block == 0) or
+ * block in {32, 64, 128, 256} take the vector kernels; anything else takes a generic kernel
+ * with the same results, which packs nothing below 8 bits (MI355Q_UNSUPPORTED, nothing written).
+ * A NaN scale has NumPy's bits: 0x7FC00000 from NaN data and from any blockwise scale,
+ * the sign of -clip from a NaN clip with block == 0 (np.clip hands back its lower bound).
  * ------------------------------------------------------------------------ */
 int32_t mi355q_requant_sym_f32(const float* x, int64_t rows, int64_t cols, int32_t block,
                                int32_t bits, const float* clip, int8_t* q_out,
@@ -105,7 +111,11 @@ int32_t mi355q_requant_sym_f32(const float* x, int64_t rows, int64_t cols, int32
 /* Same, over `count` equally shaped weight buffers in ONE launch (model-level
  * batching of ParamsGenerator's per-op loop, ref: params_generator.py:110-183).
  * The pointer tables themselves live in device memory. Any output table may be
- * NULL (that output is skipped for all tensors); clip is not supported here. */
+ * NULL (that output is skipped for all tensors); clip is not supported here.
+ * The tables cannot be read on the host, so nothing about the buffers is checked:
+ * every x must be 16-byte aligned, and every q / packed buffer aligned to the
+ * widest store of the kernel (8 bytes always suffice; equally shaped consecutive
+ * slices of one 16-byte aligned allocation comply on every route). */
 int32_t mi355q_requant_sym_f32_batched(const float* const* x_ptrs, int32_t count,
                                        int64_t rows, int64_t cols, int32_t block,
                                        int32_t bits, int8_t* const* q_ptrs,
@@ -118,7 +128,8 @@ int32_t mi355q_requant_sym_f32_batched(const float* const* x_ptrs, int32_t count
  * needs no host-to-device copy of its tables in front of its launch -- on an in-order stream that copy's completion
  * signal, not its few hundred bytes, costs ~10 us per launch against 14 us of kernel per 4096 x 4096 buffer. What
  * requant_queue issues for the resident weights of ParamsGenerator's per-op loop (ref: params_generator.py:162-183).
- * Inputs must be 16-byte aligned (outputs as in the device-table form); entries of x / scale tables must not be NULL. */
+ * Inputs must be 16-byte aligned (outputs as in the device-table form; both are checked here and MI355Q_BAD_ARG names
+ * the entry); entries of x / scale tables must not be NULL. */
 int32_t mi355q_requant_sym_f32_batched_hostptrs(const float* const* x_ptrs_host, int32_t count,
                                                 int64_t rows, int64_t cols, int32_t block,
                                                 int32_t bits, int8_t* const* q_ptrs_host,

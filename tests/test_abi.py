@@ -74,6 +74,76 @@ def test_dequantize_scale_and_difference_arguments_without_gpu(lib):
   assert st == 0   # empty tensor is a no-op
 
 
+def test_requant_argument_validation_without_gpu(lib):
+  """The three fused requantization entry points: everything that is refused, or is a no-op, before a launch. Host
+  buffers stand in for device pointers; the host tables of the hostptrs form are real."""
+  import ctypes
+  buf = ctypes.create_string_buffer(256)
+  base = (ctypes.addressof(buf) + 15) & ~15
+  p = ctypes.c_void_p(base)
+  single = lambda rows, cols, block, bits, x=p, q=None, packed=None, scale=p: lib.mi355q_requant_sym_f32(  # noqa: E731
+      x, rows, cols, block, bits, None, q, packed, scale, None, None)
+  err = lib.mi355q_last_error
+
+  def table(*addrs):
+    return (ctypes.c_void_p * len(addrs))(*addrs)
+
+  forms = {"tables": lib.mi355q_requant_sym_f32_batched, "hostptrs": lib.mi355q_requant_sym_f32_batched_hostptrs}
+  good = table(base, base + 64)
+
+  def batched(form, count, rows, cols, block, bits, x=good, q=None, packed=None, scale=good):
+    return forms[form](x, count, rows, cols, block, bits, q, packed, scale, None, None)
+
+  # bits
+  assert single(4, 128, 0, 3) == -3 and b"bits must be 8, 4 or 2 (got 3)" in err()
+  for form in forms:
+    assert batched(form, 2, 4, 128, 0, 3) == -3 and b"bits must be 8, 4 or 2 (got 3)" in err()
+  # packed output of a sub-byte width needs whole bytes
+  assert single(3, 3, 0, 4, packed=p) == -2 and b"packed output needs numel % 2 == 0" in err()
+  assert single(3, 3, 0, 2, packed=p) == -2 and b"packed output needs numel % 4 == 0" in err()
+  assert single(3, 6, 0, 2, packed=p) == -2 and b"packed output needs numel % 4 == 0" in err()
+  for form in forms:
+    assert batched(form, 2, 3, 3, 0, 4, packed=good) == -2 and b"packed output needs numel % 2 == 0" in err()
+    assert batched(form, 2, 3, 6, 0, 2, packed=good) == -2 and b"packed output needs numel % 4 == 0" in err()
+  # shapes
+  assert single(-1, 128, 0, 8) == -1 and b"negative shape" in err()
+  assert single(4, 128, -32, 8) == -1 and b"negative block size" in err()
+  for form in forms:
+    assert batched(form, 2, 4, 130, 128, 4) == -2 and b"is not divisible by block size 128" in err()
+  # empty requests are no-ops, whatever the pointers
+  assert single(0, 128, 0, 8, x=None, scale=None) == 0 and err() == b""
+  assert single(4, 0, 0, 8, x=None, scale=None) == 0 and err() == b""
+  for form in forms:
+    assert batched(form, 0, 4, 128, 0, 8, x=None, scale=None) == 0 and err() == b""
+    assert batched(form, 2, 0, 128, 0, 8, x=None, scale=None) == 0 and err() == b""
+    assert batched(form, 2, 4, 0, 0, 8, x=None, scale=None) == 0 and err() == b""
+  # null x / scale (tables)
+  assert single(4, 128, 0, 8, x=None) == -1 and b"must not be null" in err()
+  assert single(4, 128, 0, 8, scale=None) == -1 and b"must not be null" in err()
+  for form in forms:
+    assert batched(form, 2, 4, 128, 0, 8, x=None) == -1 and b"must not be null" in err()
+    assert batched(form, 2, 4, 128, 0, 8, scale=None) == -1 and b"must not be null" in err()
+  # count
+  for form in forms:
+    assert batched(form, -1, 4, 128, 0, 8) == -1 and b"count" in err()
+  assert batched("tables", 65536, 4, 128, 0, 8) == -1 and b"count must be in [0, 65535]" in err()
+  # entries of the host tables: null, a 4-byte offset input, an output off the kernel's store width
+  three = lambda i, bad: table(*[bad if j == i else base + 16 * j for j in range(3)])  # noqa: E731
+  for i in range(3):
+    assert batched("hostptrs", 3, 4, 128, 0, 8, x=three(i, None), scale=three(3, 0)) == -1
+    assert b"null buffer pointer" in err() and b"(entry %d)" % i in err()
+    assert batched("hostptrs", 3, 4, 128, 0, 8, x=three(3, 0), scale=three(i, None)) == -1
+    assert b"null buffer pointer" in err() and b"(entry %d)" % i in err()
+    assert batched("hostptrs", 3, 4, 128, 0, 8, x=three(i, base + 16 * i + 4), scale=three(3, 0)) == -1
+    assert b"16-byte aligned inputs" in err() and b"(entry %d)" % i in err()
+    for kw in (dict(q=three(i, base + 16 * i + 2)), dict(packed=three(i, base + 16 * i + 2))):
+      assert batched("hostptrs", 3, 4, 128, 0, 8, x=three(3, 0), scale=three(3, 0), **kw) == -1
+      assert b"output not aligned" in err() and b"entry %d)" % i in err()
+    # the groups kernels store two dwords of int8 at a time
+    assert batched("hostptrs", 3, 4, 128, 32, 8, x=three(3, 0), scale=three(3, 0), q=three(i, base + 16 * i + 4)) == -1
+    assert b"output not aligned" in err() and b"entry %d)" % i in err()
+
+
 def test_product_path_refuses_to_run_without_gpu(lib):
   import torch
   if torch.cuda.is_available():
