@@ -42,6 +42,12 @@ PROTOTYPES = {
     "mi355q_act_minmax_workspace_bytes": (c_size, [c_i32]),
     "mi355q_act_minmax_f32": (c_i32, [c_ptr, c_ptr, c_i32, c_f32, c_f32, c_i32, c_ptr, c_ptr,
                                       c_size, c_ptr]),
+    "mi355q_hist_stats_workspace_bytes": (c_size, [c_i64]),
+    "mi355q_hist_stats_f32": (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                      c_size, c_ptr]),
+    "mi355q_hist_bins_workspace_bytes": (c_size, [c_i64]),
+    "mi355q_hist_bins_f32": (c_i32, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                     c_i64, c_i32, c_ptr, c_i64, c_ptr, c_size, c_ptr]),
     "mi355q_octav_workspace_bytes": (c_size, [c_i64, c_i32]),
     "mi355q_octav_rows_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
     "mi355q_octav_clip_f32": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_i32, c_f32, c_i32, c_i32,

@@ -309,6 +309,82 @@ def act_minmax_entries(pointers, lengths, lo: float = -3e38, hi: float = 3e38) -
   return out
 
 
+def _hist_tables(pointers, outers, channels, inners, i: int, m: int):
+  """The entry tables of entries i .. i + m: three queued copies out of the pinned ring. -> (ptr, outer, channels, inner,
+  slot0) device rows, the chunk's slot count and its largest element count."""
+  ch = [int(c) for c in channels[i:i + m]]
+  slot0, total = [], 0
+  for c in ch:
+    slot0.append(total)
+    total += c
+  a = _table_to_device(pointers[i:i + m], outers[i:i + m])
+  b = _table_to_device(ch, inners[i:i + m])
+  c = _table_to_device(slot0, slot0)
+  numel = max(int(o) * int(k) * int(n) for o, k, n in zip(outers[i:i + m], ch, inners[i:i + m]))
+  return (a[0], a[1], b[0], b[1], c[0]), total, numel
+
+
+def hist_stats_entries(pointers, outers, channels, inners):
+  """Finite min, finite max and finite count of every (entry, channel) of a table of float32 tensors whose memory the
+  caller keeps alive until the launch has run; entry k is seen as [outers[k], channels[k], inners[k]] and owns channels[k]
+  consecutive slots. -> (float32 [S], float32 [S], int64 [S]) on the device; +inf / -inf / 0 where nothing is finite.
+  ref: utils/histogram_utils.py:145-146, 404-416."""
+  rt.require_gpu()
+  n = len(pointers)
+  slots = sum(int(c) for c in channels)
+  mn, mx = rt.empty((slots,), torch.float32), rt.empty((slots,), torch.float32)
+  cnt = rt.empty((slots,), torch.int64)
+  L = _ffi.lib()
+  done = 0
+  for i in range(0, n, _TABLE_CAPACITY):
+    m = min(_TABLE_CAPACITY, n - i)
+    tabs, s, numel = _hist_tables(pointers, outers, channels, inners, i, m)
+    nbytes = L.mi355q_hist_stats_workspace_bytes(s)
+    ws = rt.empty((max(nbytes, 1),), torch.uint8)
+    _ffi.check(L.mi355q_hist_stats_f32(*[rt.ptr(t) for t in tabs], m, s, numel, rt.ptr(mn[done:done + s]),
+                                       rt.ptr(mx[done:done + s]), rt.ptr(cnt[done:done + s]), rt.ptr(ws), nbytes,
+                                       rt.stream_ptr()))
+    done += s
+  return mn, mx, cnt
+
+
+def hist_bins_entries(pointers, outers, channels, inners, lower_bound, bin_width, n_bins, precision: int = 0):
+  """Bin counts of the same kind of table: slot s (in table order) counts its finite elements into n_bins[s] bins from
+  lower_bound[s] in steps of bin_width[s]; n_bins[s] == 0 skips the slot. precision: 0 float32 arithmetic, 1 float32
+  subtraction and float64 division, 2 float64 (include/mi355q.h). -> (int64 [sum(n_bins)] on the device, the row offsets
+  as an int64 ndarray). ref: utils/histogram_utils.py:157-164."""
+  rt.require_gpu()
+  n = len(pointers)
+  nb = np.ascontiguousarray(n_bins, dtype=np.int64)
+  slots = sum(int(c) for c in channels)
+  if nb.shape != (slots,) or len(lower_bound) != slots or len(bin_width) != slots:
+    raise ValueError("lower_bound, bin_width and n_bins need one entry per (entry, channel)")
+  if nb.size and int(nb.min()) < 0:
+    raise ValueError("n_bins must not be negative")
+  offsets = np.zeros(slots, np.int64)
+  if slots > 1:
+    np.cumsum(nb[:-1], out=offsets[1:])
+  total = int(nb.sum())
+  out = torch.zeros((max(total, 1),), dtype=torch.int64, device=rt.device())
+  if total == 0:
+    return out[:0], offsets
+  real = torch.from_numpy(np.stack([np.asarray(lower_bound, np.float64), np.asarray(bin_width, np.float64)])).to(rt.device())
+  whole = torch.from_numpy(np.stack([nb, offsets])).to(rt.device())
+  L = _ffi.lib()
+  done = 0
+  for i in range(0, n, _TABLE_CAPACITY):
+    m = min(_TABLE_CAPACITY, n - i)
+    tabs, s, numel = _hist_tables(pointers, outers, channels, inners, i, m)
+    nbytes = L.mi355q_hist_bins_workspace_bytes(s)
+    ws = rt.empty((max(nbytes, 1),), torch.uint8)
+    _ffi.check(L.mi355q_hist_bins_f32(*[rt.ptr(t) for t in tabs], m, s, numel, rt.ptr(real[0, done:done + s]),
+                                      rt.ptr(real[1, done:done + s]), rt.ptr(whole[0, done:done + s]),
+                                      rt.ptr(whole[1, done:done + s]), int(nb[done:done + s].max()), int(precision),
+                                      rt.ptr(out), total, rt.ptr(ws), nbytes, rt.stream_ptr()))
+    done += s
+  return out[:total], offsets
+
+
 _OCTAV_MODE = [None]          # None: MI355Q_OCTAV_FAST decides; "exact" / "fast" inside octav_mode()
 
 

@@ -216,6 +216,49 @@ int32_t mi355q_act_minmax_f32(const float* const* x_ptrs, const int64_t* numel,
                               void* stream);
 
 /* ------------------------------------------------------------------------
+ * Activation histograms -- the two per-element passes of DynamicHistogram.
+ * ref: utils/histogram_utils.py:139-164 (_DynamicHistogram1D.add), :396-416 (the
+ *      isfinite filter of DynamicHistogram.add)
+ *
+ * Both take `count` float32 tensors as device tables: x_ptrs and the
+ * [outer, channels, inner] view of each (channels == 1: one histogram per
+ * tensor), plus slot0, the first of the entry's `channels` consecutive slots.
+ * `slots` is the number of slots of the whole table, max_numel the element
+ * count of the largest entry (it only sizes the grid).
+ *
+ * mi355q_hist_stats_f32: per slot the minimum and maximum of the finite
+ * elements (+inf / -inf when there is none) and their number. NaN and +-inf
+ * are left out by a finiteness test.
+ *
+ * mi355q_hist_bins_f32: per slot with n_bins > 0, every finite element adds one
+ * to counts_out[row_offset + clip(int32(floor((x - lower_bound) / bin_width)),
+ * 0, n_bins - 1)]; a slot with n_bins == 0 is skipped. counts_out (out_len
+ * int64) is added to, not cleared; a row that does not lie inside it, or an
+ * n_bins above n_max (the largest n_bins of the table), is skipped.
+ *   precision 0: float32 subtraction and division (a float32 state);
+ *             1: float32 subtraction, float64 division;
+ *             2: both in float64 (the element is widened first).
+ * lower_bound / bin_width travel as doubles and are rounded to float32 where
+ * the arithmetic is float32. The quotient is the IEEE one (no reciprocal).
+ * ------------------------------------------------------------------------ */
+size_t mi355q_hist_stats_workspace_bytes(int64_t slots);
+int32_t mi355q_hist_stats_f32(const float* const* x_ptrs, const int64_t* outer,
+                              const int64_t* channels, const int64_t* inner,
+                              const int64_t* slot0, int32_t count, int64_t slots,
+                              int64_t max_numel, float* min_out, float* max_out,
+                              int64_t* count_out, void* workspace, size_t workspace_bytes,
+                              void* stream);
+size_t mi355q_hist_bins_workspace_bytes(int64_t slots);
+int32_t mi355q_hist_bins_f32(const float* const* x_ptrs, const int64_t* outer,
+                             const int64_t* channels, const int64_t* inner,
+                             const int64_t* slot0, int32_t count, int64_t slots,
+                             int64_t max_numel, const double* lower_bound,
+                             const double* bin_width, const int64_t* n_bins,
+                             const int64_t* row_offset, int64_t n_max, int32_t precision,
+                             int64_t* counts_out, int64_t out_len, void* workspace,
+                             size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------
  * K5 -- OCTAV clipping constants, NumPy-order exact.
  * ref: algorithms/uniform_quantize/octav.py:30-112 (_guess_clipping_with_octav)
  *
