@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "compare_target.h"
 
 namespace mi355q {
 namespace {
@@ -93,38 +94,6 @@ __device__ __forceinline__ float nan_to_num(float v) {
   if (v == __builtin_inff()) return 1e9f;
   if (v == -__builtin_inff()) return -1e9f;
   return v;
-}
-
-// Target element e as NumPy's get_tensor_data + np.asarray(..., np.float32) sees it.
-__device__ __forceinline__ float load_target(const mi355q_compare_pair& p, int64_t e) {
-  int32_t q;
-  switch (p.target_kind) {
-    case MI355Q_CMP_F32: return static_cast<const float*>(p.target)[e];
-    case MI355Q_CMP_F16: return static_cast<float>(static_cast<const _Float16*>(p.target)[e]);
-    case MI355Q_CMP_BF16: return u2f(static_cast<uint32_t>(static_cast<const uint16_t*>(p.target)[e]) << 16);
-    case MI355Q_CMP_I8: q = static_cast<const int8_t*>(p.target)[e]; break;
-    case MI355Q_CMP_I16: q = static_cast<const int16_t*>(p.target)[e]; break;
-    case MI355Q_CMP_I32: q = static_cast<const int32_t*>(p.target)[e]; break;
-    case MI355Q_CMP_I4: {
-      const uint32_t byte = static_cast<const uint8_t*>(p.target)[e >> 1];
-      q = static_cast<int32_t>(byte << (28 - 4 * (e & 1))) >> 28;   // element 0 in the low nibble
-      break;
-    }
-    default: {  // MI355Q_CMP_I2
-      const uint32_t byte = static_cast<const uint8_t*>(p.target)[e >> 2];
-      q = static_cast<int32_t>(byte << (30 - 2 * (e & 3))) >> 30;
-      break;
-    }
-  }
-  const int64_t c = p.channels == 1 ? 0 : (e / p.inner) % p.channels;
-  // NumPy subtracts in the promoted integer type of (q, zero_point) and wraps (int8 - int8 stays int8)
-  int32_t d = static_cast<int32_t>(static_cast<uint32_t>(q) - static_cast<uint32_t>(p.zero_point ? p.zero_point[c] : 0));
-  if (p.diff_bits == 8) d = static_cast<int8_t>(d);
-  else if (p.diff_bits == 16) d = static_cast<int16_t>(d);
-  const float s = p.scale[c];
-  // int8 / int16 * float32 is a float32 product; int32 * float32 is float64, cast to float32 afterwards
-  if (p.diff_bits == 32) return static_cast<float>(static_cast<double>(d) * static_cast<double>(s));
-  return static_cast<float>(d) * s;
 }
 
 struct Elem {

@@ -186,16 +186,21 @@ def constant_plans(reference_model, target_model, signature_key: Optional[str] =
     if plan is None:
       continue
     if plan.kind in ("i4", "i2", "i8", "i16", "i32") and plan.dequantized and plan.scale is None:
-      q = target.quantization
-      sc = tgt_tensors[int(q.details.scales)]
-      plan.scale = np.asarray(tfl_flatbuffer_utils.get_tensor_data(sc, tgt.buffers), np.float32).ravel()
-      plan.zero_point = None
-      if len(target.shape) != 2 or plan.channels != len(plan.scale):
-        raise ValueError(
-            f"blockwise constant {name!r}: expected a 2-D weight with one scale per block of {plan.inner} along its"
-            f" last axis, got shape {list(target.shape)} and {len(plan.scale)} scales")
+      _read_blockwise_scales(plan, tgt, tgt_tensors, target)
     plans.append(plan)
   return plans
+
+
+def _read_blockwise_scales(plan: ConstantPlan, tgt, tgt_tensors, target) -> None:
+  """The scales of a blockwise constant are a tensor of their own in the target model."""
+  q = target.quantization
+  sc = tgt_tensors[int(q.details.scales)]
+  plan.scale = np.asarray(tfl_flatbuffer_utils.get_tensor_data(sc, tgt.buffers), np.float32).ravel()
+  plan.zero_point = None
+  if len(target.shape) != 2 or plan.channels != len(plan.scale):
+    raise ValueError(
+        f"blockwise constant {plan.name!r}: expected a 2-D weight with one scale per block of {plan.inner} along its"
+        f" last axis, got shape {list(target.shape)} and {len(plan.scale)} scales")
 
 
 def _device_target(plan: ConstantPlan):
@@ -453,3 +458,204 @@ def compare_model(reference_model: bytes, target_model: bytes,
       aggregated[nm] = {mt.value: float(np.mean([row[i] for row in rows])) for i, mt in enumerate(error_metrics)}
     result.add_new_signature_results(error_metrics, aggregated, signature_key, validate_output_tensors_only)
   return result
+
+
+# ----------------------------------------------------------------------------- layer output error
+# For a FULLY_CONNECTED op y = x W^T, with H = (2/n) X^T X over the calibration inputs (the statistic GPTQ calibration
+# keeps per FULLY_CONNECTED input) and dW = W - dequant(W^):
+#   (1/n) ||X dW^T||_F^2 = 1/2 tr(dW H dW^T) = 1/2 Sum_r d_r H d_r^T
+# the layer's output error over the whole calibration set, with no run of the model (csrc/layer_error.hip).
+_FULLY_CONNECTED = 9
+SKIP_NO_HESSIAN = "no Hessian for the input"
+SKIP_WEIGHT = "weight is not a constant 2-D tensor"
+SKIP_ORDER = "Hessian order differs from the weight's reduction dimension"
+SKIP_TARGET = "target constant missing or of another size"
+SKIP_INPUT = "the quantized op reads a transformed input"
+
+
+def _as_model(model) -> Any:
+  return model if hasattr(model, "subgraphs") else _model(model)
+
+
+def _fully_connected_ops(m, sg_index: int):
+  """(op, input 0 name, weight tensor, output name) of every FULLY_CONNECTED op of a subgraph."""
+  sg = m.subgraphs[sg_index]
+  out = []
+  for op in sg.operators or []:
+    if int(m.operatorCodes[op.opcodeIndex].builtinCode) != _FULLY_CONNECTED or len(op.inputs) < 2:
+      continue
+    out.append((op, schema.tensor_name(sg.tensors[op.inputs[0]]), sg.tensors[op.inputs[1]],
+                schema.tensor_name(sg.tensors[op.outputs[0]])))
+  return out
+
+
+def layer_hessians(float_model, samples: Iterable[dict], signature_key: Optional[str] = None) -> dict[str, dict]:
+  """{input tensor name: {"hessian": HessianAccumulator, "num_samples": n}} for every FULLY_CONNECTED op whose
+  input 0 appears in `samples`, the {tensor name: array or device tensor} maps that `calibrate` takes. The same
+  accumulators as GPTQ calibration: H = (2/n) X^T X, n = the samples' leading dimensions. For recipes whose
+  calibration keeps no Hessians (min/max, OCTAV, MSE, ...)."""
+  import torch
+  from . import runtime as rt
+  from .algorithms.uniform_quantize import gptq
+  m = _as_model(float_model)
+  sg_index, _ = _signature_subgraph(m, signature_key)
+  names = {name for _, name, _, _ in _fully_connected_ops(m, sg_index)}
+  out: dict[str, dict] = {}
+  for sample in samples:
+    for name in names:
+      if name not in sample:
+        continue
+      x = rt.on_device(rt.resident_sample(sample[name]), torch.float32)
+      n = int(x.shape[0]) if x.dim() > 0 else 1
+      x2d = x.reshape(-1, x.shape[-1] if x.dim() > 0 else 1)
+      entry = out.get(name)
+      if entry is None:
+        entry = out[name] = {"hessian": gptq.HessianAccumulator(x2d.shape[1]), "num_samples": 0}
+      entry["hessian"].add(x2d, n)
+      entry["num_samples"] += n
+  for entry in out.values():
+    entry["hessian"].finalize()
+    entry["num_samples"] = np.array(entry["num_samples"])
+  return out
+
+
+class LayerErrorKernels:
+  """The device side of compare_layer_outputs: where the operands live and the two kernels."""
+
+  def weight(self, values: np.ndarray):
+    from . import runtime as rt
+    return rt.to_device(values)
+
+  def delta(self, reference, plan: ConstantPlan):
+    from . import ops
+    return ops.weight_delta(reference, _device_target(plan))
+
+  def hessian(self, stat):
+    """(float32 [d, d] whose lower triangle is valid, alpha) with H = alpha * product."""
+    import torch
+    from . import runtime as rt
+    form = stat.product_form() if hasattr(stat, "product_form") else None
+    if form is not None:
+      return form
+    # a finished float64 Hessian (loaded, resumed): rounded to float32 once, on the device
+    return rt.on_device(stat, torch.float64).to(torch.float32), 1.0
+
+  def quadform(self, a, rows: int, d: int, product, alpha: float) -> np.ndarray:
+    from . import ops
+    return ops.quadform_rows(a.view(rows, d), product, alpha).cpu().numpy()
+
+
+class LayerOutputComparison:
+  """Per FULLY_CONNECTED op (keyed by its output tensor's name): how far the quantized weight moves the op's
+  output over the calibration set. `results[name]` holds `weight`, `input`, `rows`, `d`, `signal`, `error`,
+  `output_mse`, `output_snr` and `per_channel_error` (float64 [rows]); `skipped[name]` is the reason an op was
+  not computed."""
+
+  def __init__(self, signature_key: Optional[str] = None):
+    self.signature_key = signature_key
+    self.results: dict[str, dict] = {}
+    self.skipped: dict[str, str] = {}
+
+  def __getitem__(self, name: str) -> dict:
+    return self.results[name]
+
+  def __contains__(self, name: str) -> bool:
+    return name in self.results
+
+  def __iter__(self):
+    return iter(self.results)
+
+  def __len__(self) -> int:
+    return len(self.results)
+
+  def as_dict(self) -> dict:
+    layers = {name: {k: v for k, v in r.items() if k != "per_channel_error"} for name, r in self.results.items()}
+    return {"signature_key": self.signature_key, "layers": layers, "skipped": dict(self.skipped)}
+
+  def save(self, save_folder: str, model_name: str) -> str:
+    """`<model_name>_layer_output_errors.json`, without the per-channel arrays."""
+    save_path = pathlib.Path(save_folder)
+    os.makedirs(str(save_path), exist_ok=True)
+    path = str(save_path / (model_name + "_layer_output_errors.json"))
+    with open(path, "w") as fh:
+      fh.write(json.dumps(self.as_dict()))
+    return path
+
+
+def compare_layer_outputs(reference_model, target_model, calibration_result: dict,
+                          signature_key: Optional[str] = DEFAULT_SIGNATURE_KEY, *,
+                          kernels: Optional[LayerErrorKernels] = None) -> LayerOutputComparison:
+  """Output error of every FULLY_CONNECTED op of the float model with a constant 2-D weight [rows, d].
+
+  With H = calibration_result[input 0's name]["hessian"] = (2/n) X^T X and dW = W - dequant(W^), the target weight
+  found BY NAME in the quantized model (so it does not matter whether a DEQUANTIZE op was inserted):
+    error  = 1/2 Sum_r d_r H d_r^T = (1/n) ||X dW^T||_F^2        signal = the same form of W
+    output_mse = error / rows     output_snr = (signal / rows) / (output_mse + 1e-9)
+  (the convention of validation_utils.signal_to_noise_ratio). The cost does not depend on the number of calibration
+  tokens, and a saved calibration result serves as well as a fresh one.
+
+  This is the weight's contribution to the op's pre-activation output: bias and fused activation do not enter, and
+  under static recipes the activations' own rounding is not included. Ops whose quantized form reads a transformed
+  activation (an inserted Hadamard rotation or OSCAR multiply) are reported in `.skipped`, not computed: their
+  stored weight lives in the transformed basis. Non-finite Hessians give non-finite results, which is no error.
+  """
+  kernels = kernels or LayerErrorKernels()
+  ref, tgt = _as_model(reference_model), _as_model(target_model)
+  sg_ref, _ = _signature_subgraph(ref, signature_key)
+  sg_tgt, _ = _signature_subgraph(tgt, signature_key)
+  tgt_sg = tgt.subgraphs[sg_tgt]
+  by_name: dict[str, Any] = {}
+  for t in tgt_sg.tensors:
+    by_name.setdefault(schema.tensor_name(t), t)
+  producer_input: dict[str, Optional[str]] = {}     # output tensor name -> name of its producer's input 0
+  for op in tgt_sg.operators or []:
+    first = schema.tensor_name(tgt_sg.tensors[op.inputs[0]]) if len(op.inputs) and op.inputs[0] >= 0 else None
+    for o in op.outputs:
+      producer_input.setdefault(schema.tensor_name(tgt_sg.tensors[o]), first)
+  out = LayerOutputComparison(signature_key)
+  hessians: dict[str, tuple] = {}
+  signals: dict[tuple, np.ndarray] = {}             # (weight name, input name) -> per-row signal
+  resident: tuple = (None, None)                    # (weight name, its device copy): one float weight at a time
+  for _, x_name, w, y_name in _fully_connected_ops(ref, sg_ref):
+    w_name = schema.tensor_name(w)
+    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 2):
+      out.skipped[y_name] = SKIP_WEIGHT
+      continue
+    rows, d = int(w.shape[0]), int(w.shape[1])
+    stat = (calibration_result.get(x_name) or {}).get("hessian") if calibration_result else None
+    if stat is None:
+      out.skipped[y_name] = SKIP_NO_HESSIAN
+      continue
+    if tuple(stat.shape) != (d, d):
+      out.skipped[y_name] = SKIP_ORDER
+      continue
+    target = by_name.get(w_name)
+    if target is None or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if producer_input.get(y_name) != x_name:
+      out.skipped[y_name] = SKIP_INPUT
+      continue
+    values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
+    plan = _target_plan(w_name, values, tgt, target)
+    if plan is None:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if plan.kind in ("i4", "i2", "i8", "i16", "i32") and plan.dequantized and plan.scale is None:
+      _read_blockwise_scales(plan, tgt, tgt_sg.tensors, target)
+    if x_name not in hessians:
+      hessians[x_name] = kernels.hessian(stat)
+    product, alpha = hessians[x_name]
+    if resident[0] != w_name:
+      resident = (w_name, kernels.weight(values))
+    w_dev = resident[1]
+    if (w_name, x_name) not in signals:
+      signals[(w_name, x_name)] = kernels.quadform(w_dev, rows, d, product, 0.5 * alpha)
+    per_row_signal = signals[(w_name, x_name)]
+    per_channel = kernels.quadform(kernels.delta(w_dev, plan), rows, d, product, 0.5 * alpha)
+    signal, error = float(np.sum(per_row_signal)), float(np.sum(per_channel))
+    mse = error / rows
+    out.results[y_name] = {"weight": w_name, "input": x_name, "rows": rows, "d": d, "signal": signal, "error": error,
+                           "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
+                           "per_channel_error": per_channel}
+  return out

@@ -968,3 +968,35 @@ def compare(pairs, median: bool = True, kl: bool = True) -> np.ndarray:
   host = res.cpu().numpy().view(COMPARE_RESULT_DTYPE)     # (synchronizes: every operand above is still alive)
   out[[i for i, (_, t) in enumerate(pairs) if t.n > 0]] = host
   return out
+
+
+def weight_delta(reference: torch.Tensor, target: CompareTarget) -> torch.Tensor:
+  """float32 [n] = reference - dequant(target), the target dequantized in registers by the rule of `compare`
+  (no nan_to_num: values pass through as they are). Does not synchronize."""
+  rt.require_gpu()
+  reference = _f32(reference).view(-1)
+  if reference.numel() != target.n:
+    raise ValueError("data1 & data2 must be of the same size")
+  out = rt.empty((target.n,), torch.float32)
+  _ffi.check(_ffi.lib().mi355q_weight_delta_f32(
+      rt.ptr(reference), rt.ptr(target.data), target.n, COMPARE_KINDS[target.kind], target.diff_bits, target.channels,
+      target.inner, rt.ptr(target.scale), rt.ptr(target.zero_point), rt.ptr(out), rt.stream_ptr()))
+  return out
+
+
+def quadform_rows(a: torch.Tensor, product: torch.Tensor, alpha: float) -> torch.Tensor:
+  """float64 [rows]: alpha * a_r Psym a_r^T for float32 a [rows, d] and the symmetric matrix whose LOWER triangle
+  is `product` (float32 [d, d], e.g. HessianAccumulator.product_form(); the upper triangle is never read and
+  `product` is not modified). Does not synchronize."""
+  rt.require_gpu()
+  a, product = _f32(a), _f32(product)
+  if a.dim() != 2 or product.dim() != 2 or product.shape[0] != product.shape[1] or product.shape[0] != a.shape[1]:
+    raise ValueError(f"expected a [rows, d] and product [d, d], got {tuple(a.shape)} and {tuple(product.shape)}")
+  rows, d = a.shape
+  out = rt.empty((rows,), torch.float64)
+  L = _ffi.lib()
+  nbytes = L.mi355q_quadform_rows_workspace_bytes(rows, d)
+  ws = rt.empty((max(nbytes, 1),), torch.uint8)
+  _ffi.check(L.mi355q_quadform_rows_f32(rt.ptr(a), rows, d, rt.ptr(product), float(alpha), rt.ptr(out), rt.ptr(ws),
+                                        nbytes, rt.stream_ptr()))
+  return out

@@ -5,7 +5,8 @@ mmap'd file), load a recipe, generate parameters through the registry (GPU kerne
 QUANTIZE_TENSOR transformation (pack + store + metadata) and serialize. Running a model (the LiteRT
 interpreter) is outside this build's scope: calibration results (QSVs) are passed in, and `validate()`
 compares the constant tensors on the GPU and takes inputs, outputs and intermediates from a
-caller-supplied `run_signature`.
+caller-supplied `run_signature`; `validate_layer_outputs()` reports the output error of every FULLY_CONNECTED op
+over the calibration set from the Hessians calibration keeps, without a run of the model.
 """
 from __future__ import annotations
 
@@ -202,6 +203,42 @@ class Quantizer:
         float_model, bytes(quantized_model), test_data, error_metrics, compare_fns=None,
         use_xnnpack=use_xnnpack, num_threads=num_threads,
         validate_output_tensors_only=validate_output_tensors_only, run_signature=run_signature)
+    if save_folder:
+      if model_name is None:
+        model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"
+      results.save(save_folder, model_name=model_name)
+    return results
+
+  def validate_layer_outputs(self, calibration_result: Optional[dict] = None, calibration_data: Optional[Any] = None,
+                             signature_key: Optional[str] = None, save_folder: Optional[str] = None,
+                             model_name: Optional[str] = None) -> model_validator.LayerOutputComparison:
+    """Output error of every FULLY_CONNECTED op of the last quantize() result over the calibration set:
+    error = 1/2 tr(dW H dW^T) = (1/n) ||X dW^T||_F^2 per op, with its signal, MSE, SNR and per-channel errors
+    (model_validator.compare_layer_outputs; no run of the model is needed).
+
+    Exactly one of `calibration_result` (what calibrate() returned for a recipe that keeps Hessians, or a loaded
+    one) and `calibration_data` (the samples calibrate() takes: a list of {tensor name: array or device tensor}, or
+    {signature key: such a list}; their Hessians are formed here) is required.
+    """
+    quantized_model = self._result.quantized_model
+    if quantized_model is None:
+      raise ValueError("No quantized model available to validate.")
+    if (calibration_result is None) == (calibration_data is None):
+      raise ValueError("validate_layer_outputs needs exactly one of calibration_result and calibration_data.")
+    if calibration_data is not None:
+      samples = calibration_data
+      if isinstance(calibration_data, dict):
+        if signature_key is not None:
+          if signature_key not in calibration_data:
+            raise ValueError(f"calibration_data has no samples for signature {signature_key!r}")
+          samples = calibration_data[signature_key]
+        elif len(calibration_data) == 1:
+          samples = next(iter(calibration_data.values()))
+        else:
+          raise ValueError("signature_key is required when calibration_data holds several signatures")
+      calibration_result = model_validator.layer_hessians(self.float_model, samples, signature_key)
+    results = model_validator.compare_layer_outputs(self.float_model, bytes(quantized_model), calibration_result,
+                                                    signature_key)
     if save_folder:
       if model_name is None:
         model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"

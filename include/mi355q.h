@@ -753,6 +753,44 @@ int32_t mi355q_compare_f32_batched(const mi355q_compare_pair* pairs, int32_t cou
                                    int32_t flags, mi355q_compare_result* results, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Layer output error of a quantized FULLY_CONNECTED weight (csrc/layer_error.hip)
+ *
+ * With H = (2/n) X^T X, the statistic GPTQ calibration keeps per FULLY_CONNECTED
+ * input, and dW = W - dequant(W^):
+ *   (1/n) ||X dW^T||_F^2 = 1/2 tr(dW H dW^T) = 1/2 Sum_r d_r H d_r^T
+ * so the layer's output error over the calibration set is one quadratic form per
+ * output channel against a matrix that is already resident.
+ *
+ * mi355q_weight_delta_f32: delta_out[e] = reference[e] - dequant(target)[e] in
+ * float32. The target is described exactly as for mi355q_compare_f32 (MI355Q_CMP_*
+ * kinds, [outer, channels, inner] scale view, the diff_bits rule, I4 / I2 packed
+ * low bits first) and dequantized in registers by the same rule. There is no
+ * nan_to_num here: values pass through as they are. n = 0 enqueues nothing.
+ *
+ * mi355q_quadform_rows_f32: out_rows[r] = alpha * a_r Psym a_r^T in FLOAT64 for
+ * a = float32 [rows, d] row-major and Psym the symmetric matrix whose LOWER
+ * triangle (j <= i) is product[i*d + j] -- the float32 product form of a Hessian
+ * accumulator. Nothing above the diagonal is ever read and nothing of `product`
+ * is written. FP32 MFMA tiles C = a L' over (128 rows x 128 columns j0), where
+ * L'[k][j] = 2 P[k][j] for k > j, P[j][j] for k = j and 0 for k < j: the K loop
+ * runs over k >= j0 only, the doubling is exact, and no 2*lower - diagonal
+ * subtraction exists. The epilogue multiplies C by the `a` tile, sums every row's
+ * 64 columns in float64 into partials[ceil(d / 64)][rows], and a second kernel
+ * adds a row's partials in index order: the result has the same bits in every
+ * run (no floating-point atomics) and there is no rows x d intermediate.
+ * |out_r - exact_r| <= (2d + 3) 2^-24 alpha Sum_ij |a_ri| |P_ij| |a_rj| to first
+ * order. Non-finite inputs give non-finite rows; rows = 0 enqueues nothing.
+ * workspace: mi355q_quadform_rows_workspace_bytes(rows, d) =
+ * rows * ceil(d / 64) * 8 rounded up to 256 bytes.
+ * ------------------------------------------------------------------------ */
+int32_t mi355q_weight_delta_f32(const float* reference, const void* target, int64_t n, int32_t target_kind,
+                                int32_t diff_bits, int64_t channels, int64_t inner, const float* scale,
+                                const int32_t* zero_point, float* delta_out, void* stream);
+size_t mi355q_quadform_rows_workspace_bytes(int64_t rows, int64_t d);
+int32_t mi355q_quadform_rows_f32(const float* a, int64_t rows, int64_t d, const float* product, double alpha,
+                                 double* out_rows, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
