@@ -248,6 +248,7 @@ __device__ __forceinline__ void batch_offset(GemmArgs<T>& g) {
     g.A += b * g.sa;
     g.B += b * g.sb;
     g.C += b * g.sc;
+    if (g.c32 != nullptr) g.c32 += b * g.sc;
   }
 }
 
@@ -483,10 +484,9 @@ __device__ __forceinline__ void gemm_fast_body(const GemmArgs<typename TL::Elem>
     while ((bi + 1) * (bi + 2) / 2 <= r) ++bi;
     while (bi * (bi + 1) / 2 > r) --bi;
     bj = r - bi * (bi + 1) / 2;
-  } else if (g.lower_only && bj > bi) {
-    return;
-  } else if (g.k_mode == 1) {
-    bi = static_cast<int>(gridDim.y) - 1 - bi;   // K grows with the tile row: longest rows first
+  } else {
+    if (g.k_mode == 1) bi = static_cast<int>(gridDim.y) - 1 - bi;   // K grows with the tile row: longest rows first
+    if (g.lower_only && bj > bi) return;   // (after the reversal: it is the tile computed that must touch the triangle)
   }
   const int i0 = bi * BM, j0 = bj * BM;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -706,7 +706,7 @@ int32_t launch_with(const GemmArgs<typename TL::Elem>& g, hipStream_t st, void* 
   using T = typename TL::Elem;
   constexpr int BM = TL::BM;
   int slices = 1;
-  if (g.batch > 1 || g.outer > 1) {
+  if (g.batch > 1 || g.outer > 1 || g.c32 != nullptr) {   // (the reducer knows neither problems nor c32)
     splitk_ws = nullptr;
   }
   if (splitk_ws != nullptr && g.k_mode == 0) {
@@ -785,7 +785,7 @@ int32_t launch_gemm(const GemmArgs<T>& g, hipStream_t st, void* splitk_ws, size_
     // the 128x128 tile pays when there are enough of them to fill the chip; k_mode offsets are
     // multiples of the block edge either way
     const long long tiles128 = static_cast<long long>((g.M + 127) / 128) * ((g.N + 127) / 128);
-    const bool splitk = splitk_ws != nullptr && g.k_mode == 0 && gemm_pick_splitk<T>(g.M, g.N, g.K, g.lower_only != 0) > 1;
+    const bool splitk = splitk_ws != nullptr && g.k_mode == 0 && g.c32 == nullptr && gemm_pick_splitk<T>(g.M, g.N, g.K, g.lower_only != 0) > 1;
     const bool whole128 = g.M % 128 == 0 && g.N % 128 == 0 && g.K % 16 == 0 && a_mode != kGeneric &&
                           b_mode != kGeneric;
 #ifndef MI355Q_BIG_MIN_TRI_TILES
@@ -856,4 +856,52 @@ extern "C" int32_t mi355q_gemm_f64(const double* A, int64_t a_i, int64_t a_k, co
                                    int64_t b_j, double* C, int64_t c_i, int64_t c_j, int64_t M, int64_t N,
                                    int64_t K, double alpha, double beta, int32_t lower_only, void* stream) {
   return gemm_entry<double>(A, a_i, a_k, B, b_k, b_j, C, c_i, c_j, M, N, K, alpha, beta, lower_only, stream);
+}
+
+namespace {
+template <typename T>
+int32_t gemm_ex_entry(const mi355q_gemm_desc* d, void* splitk_ws, size_t splitk_ws_bytes, void* stream) {
+  clear_error();
+  if (!d) return fail(MI355Q_BAD_ARG, "null descriptor");
+  if (d->M < 0 || d->N < 0 || d->K < 0) return fail(MI355Q_BAD_ARG, "negative shape");
+  if (d->M > 0x7FFFFFFF || d->N > 0x7FFFFFFF || d->K > 0x7FFFFFFF) return fail(MI355Q_UNSUPPORTED, "dimension too large");
+  if (d->k_mode < 0 || d->k_mode > 3) return fail(MI355Q_BAD_ARG, "k_mode must be 0, 1, 2 or 3 (got %d)", d->k_mode);
+  if (d->lower_only != 0 && d->lower_only != 1 && d->lower_only != 3)
+    return fail(MI355Q_BAD_ARG, "lower_only must be 0, 1 or 3 (got %d)", d->lower_only);
+  if (d->batch < 0 || d->outer < 0) return fail(MI355Q_BAD_ARG, "negative batch count");
+  if (d->c32 != nullptr && d->beta != 0.0) return fail(MI355Q_BAD_ARG, "a float32 output (c32) needs beta == 0");
+  if (d->M == 0 || d->N == 0) return MI355Q_OK;
+  if (!d->A || !d->B || !d->C) return fail(MI355Q_BAD_ARG, "null pointer");
+  const long long problems = static_cast<long long>(d->batch > 1 ? d->batch : 1) * (d->outer > 1 ? d->outer : 1);
+  if (problems > 65535) return fail(MI355Q_UNSUPPORTED, "batch * outer must be at most 65535 (grid.z)");
+  GemmArgs<T> g{static_cast<const T*>(d->A), d->a_i, d->a_k, static_cast<const T*>(d->B), d->b_k, d->b_j,
+                static_cast<T*>(d->C), d->c_i, d->c_j, static_cast<int>(d->M), static_cast<int>(d->N),
+                static_cast<int>(d->K), static_cast<T>(d->alpha), static_cast<T>(d->beta), d->lower_only, d->k_mode,
+                d->batch, d->sa, d->sb, d->sc, d->c32, d->outer, d->oa, d->ob, d->oc, d->oc32};
+  return launch_gemm<T>(g, as_stream(stream), splitk_ws, splitk_ws != nullptr ? splitk_ws_bytes : 0);
+}
+
+template <typename T>
+size_t gemm_ex_workspace(int64_t M, int64_t N, int64_t K, int32_t lower_only) {
+  if (M <= 0 || N <= 0 || K <= 0 || M > 0x7FFFFFFF || N > 0x7FFFFFFF || K > 0x7FFFFFFF) return 0;
+  return gemm_splitk_workspace_bytes<T>(static_cast<int>(M), static_cast<int>(N), static_cast<int>(K), lower_only != 0);
+}
+}  // namespace
+
+extern "C" size_t mi355q_gemm_splitk_workspace_bytes_f32(int64_t M, int64_t N, int64_t K, int32_t lower_only) {
+  return gemm_ex_workspace<float>(M, N, K, lower_only);
+}
+
+extern "C" size_t mi355q_gemm_splitk_workspace_bytes_f64(int64_t M, int64_t N, int64_t K, int32_t lower_only) {
+  return gemm_ex_workspace<double>(M, N, K, lower_only);
+}
+
+extern "C" int32_t mi355q_gemm_ex_f32(const mi355q_gemm_desc* desc, void* splitk_ws, size_t splitk_ws_bytes,
+                                      void* stream) {
+  return gemm_ex_entry<float>(desc, splitk_ws, splitk_ws_bytes, stream);
+}
+
+extern "C" int32_t mi355q_gemm_ex_f64(const mi355q_gemm_desc* desc, void* splitk_ws, size_t splitk_ws_bytes,
+                                      void* stream) {
+  return gemm_ex_entry<double>(desc, splitk_ws, splitk_ws_bytes, stream);
 }

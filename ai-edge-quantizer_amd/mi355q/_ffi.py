@@ -64,6 +64,10 @@ PROTOTYPES = {
                                 c_i64, c_i64, c_i64, c_f32, c_f32, c_i32, c_ptr]),
     "mi355q_gemm_f64": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i64,
                                 c_i64, c_i64, c_i64, c_f64, c_f64, c_i32, c_ptr]),
+    "mi355q_gemm_splitk_workspace_bytes_f32": (c_size, [c_i64, c_i64, c_i64, c_i32]),
+    "mi355q_gemm_splitk_workspace_bytes_f64": (c_size, [c_i64, c_i64, c_i64, c_i32]),
+    "mi355q_gemm_ex_f32": (c_i32, [c_ptr, c_ptr, c_size, c_ptr]),
+    "mi355q_gemm_ex_f64": (c_i32, [c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_gptq_xtx_workspace_bytes": (c_size, [c_i64, c_i64]),
     "mi355q_gptq_xtx_f32": (c_i32, [c_ptr, c_i64, c_i64, c_f64, c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_gptq_xtx_accum_workspace_bytes": (c_size, [c_i64, c_i64]),
@@ -129,6 +133,16 @@ PROTOTYPES = {
     "mi355q_device_alloc": (c_i32, [c_size, ctypes.POINTER(ctypes.c_void_p)]),
     "mi355q_device_free": (c_i32, [c_ptr]),
 }
+
+
+class GemmDesc(ctypes.Structure):
+  """mi355q_gemm_desc of include/mi355q.h, field for field."""
+  _fields_ = [("A", c_ptr), ("a_i", c_i64), ("a_k", c_i64), ("B", c_ptr), ("b_k", c_i64), ("b_j", c_i64),
+              ("C", c_ptr), ("c_i", c_i64), ("c_j", c_i64), ("M", c_i64), ("N", c_i64), ("K", c_i64),
+              ("alpha", c_f64), ("beta", c_f64), ("lower_only", c_i32), ("k_mode", c_i32),
+              ("batch", c_i32), ("outer", c_i32), ("sa", c_i64), ("sb", c_i64), ("sc", c_i64),
+              ("oa", c_i64), ("ob", c_i64), ("oc", c_i64), ("oc32", c_i64), ("c32", c_ptr)]
+
 
 STATUS_NAMES = {0: "OK", -1: "BAD_ARG", -2: "BAD_SHAPE", -3: "UNSUPPORTED", -4: "HIP_ERROR",
                 -5: "RCCL_ERROR", -6: "IO_ERROR"}

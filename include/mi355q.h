@@ -352,6 +352,48 @@ int32_t mi355q_gemm_f64(const double* A, int64_t a_i, int64_t a_k, const double*
                         int64_t b_j, double* C, int64_t c_i, int64_t c_j, int64_t M, int64_t N,
                         int64_t K, double alpha, double beta, int32_t lower_only, void* stream);
 
+/* The same contraction with every argument of the launcher the GPTQ entry points below use
+ * (csrc/gemm.h), so that each of its routes can be driven and checked on its own.
+ *   lower_only  0: all of C; 1 or 3: only j <= i is written (1 launches a triangular grid when
+ *               M == N, 3 a square grid with early exit); everything above the diagonal is kept.
+ *   k_mode      a promise about zeros that lets a tile skip part of K; the skipped range is
+ *               never read. With E the tile edge of the kernel that runs (64 or 128) and
+ *               i0 / j0 the first row / column of a tile:
+ *               0: nothing skipped;
+ *               1: A(i,k) == 0 for k > i                            -> k < i0 + E;
+ *               2: A(i,k) == 0 for k < i and B(k,j) == 0 for k < j  -> k >= max(i0, j0);
+ *               3: B(k,j) == 0 for k < j                            -> k >= j0.
+ *   batch > 1   that many problems of this shape in one launch; problem b's operands start
+ *               sa / sb / sc elements after those of problem b - 1 (c32: sc floats).
+ *   outer > 1   another batch around it (max(batch, 1) * outer problems), steps oa / ob / oc
+ *               (oc32 floats for c32). The kernel is chosen from the single problem, so the
+ *               results have the bits of separate launches.
+ *   c32         not NULL (needs beta == 0): alpha * A.B is stored there as float32
+ *               with C's strides and C is left alone (it must still be non-null).
+ * splitk_ws / splitk_ws_bytes: optional. With at least mi355q_gemm_splitk_workspace_bytes_*()
+ * bytes a long-K product of few tiles is split along K into the workspace and its slices are
+ * added in a fixed order (deterministic); with less, or NULL, or batch / outer / c32 / a k_mode
+ * other than 0, the product runs unsplit. 0 bytes = this shape is never split. */
+typedef struct mi355q_gemm_desc {
+  const void* A;
+  int64_t a_i, a_k;
+  const void* B;
+  int64_t b_k, b_j;
+  void* C;
+  int64_t c_i, c_j;
+  int64_t M, N, K;
+  double alpha, beta;
+  int32_t lower_only, k_mode;
+  int32_t batch, outer;
+  int64_t sa, sb, sc;
+  int64_t oa, ob, oc, oc32;
+  float* c32;
+} mi355q_gemm_desc;
+size_t mi355q_gemm_splitk_workspace_bytes_f32(int64_t M, int64_t N, int64_t K, int32_t lower_only);
+size_t mi355q_gemm_splitk_workspace_bytes_f64(int64_t M, int64_t N, int64_t K, int32_t lower_only);
+int32_t mi355q_gemm_ex_f32(const mi355q_gemm_desc* desc, void* splitk_ws, size_t splitk_ws_bytes, void* stream);
+int32_t mi355q_gemm_ex_f64(const mi355q_gemm_desc* desc, void* splitk_ws, size_t splitk_ws_bytes, void* stream);
+
 /* ------------------------------------------------------------------------
  * K8 -- GPTQ Hessian of one calibration tensor: hessian_out (FLOAT64 [d,d]) =
  * alpha * (X^T X), X = float32 [n, d] (tokens x channels), X^T X accumulated in
