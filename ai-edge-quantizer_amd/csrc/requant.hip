@@ -22,21 +22,36 @@ namespace {
 using namespace requant;
 
 // Tuning choices; tools/kbench/kbench.hip times the alternatives on MI355X with
-// interleaved rounds (profiles/r01_kbench_variants.txt):
-//   * rows kernel: non-temporal loads/stores (x is read once, q never re-read):
-//     72.7 % -> 76.6 % of 8 TB/s on C2;
+// interleaved rounds (profiles/r01_kbench_variants.txt, profiles/requant_rows_wide_stores.txt):
+//   * rows kernel: non-temporal loads, and non-temporal stores where a word leaves per store (x is read once,
+//     q never re-read): 72.7 % -> 76.6 % of 8 TB/s on C2;
+//   * rows that fill rows<256, R> exactly (4096, 8192, 16384 columns) take requant_rows_wide_kernel: every wave
+//     owns a contiguous run of the row, and the int8 words go through a wave-private LDS slab to leave as 16-byte
+//     stores, PLAIN ones (profiles/requant_rows_wide_stores.txt): about 220 -> 200 us on C2 (76 % -> 84 %),
+//     223 -> 201 us at 8192 and 234 -> 208 us at 16384 columns. The same stores non-temporal gain nothing, 8-byte
+//     pairs without LDS lose everywhere, and on rows that leave lanes of a wave without a 16-byte piece (3072,
+//     11008 columns) an exchange with ragged ends lost 3 - 15 % to the store per word: those variants live in
+//     tools/kbench/rows_variants.h, and every other width keeps requant_rows_kernel as it was;
 //   * blockwise kernel: every lane owns 8 consecutive floats (CL = 2) so packed
 //     int4 leaves as full dwords (55 % -> 72 %); for sub-byte outputs the exact
 //     reciprocal path (requant_kernels.h, one IEEE division per block instead of
 //     one per element) adds another ~4 points; nt does not help there;
 //   * int8 blockwise output: CL = 2 with two tiles in flight.
 constexpr bool kRowsNT = true;
+constexpr bool kRowsWideNTStores = false;
+// Which launches take requant_rows_wide_kernel: rows that fill rows<256, R> exactly (4096, 8192, 16384 columns),
+// when int8 words are asked for (q at any bit width, or 8-bit packed). A sub-byte packed output alone gains nothing
+// measurable from it (level at 8192 and 16384 columns, slower at 4096) and keeps requant_rows_kernel.
+template <int BITS>
+inline bool rows_wide(int64_t cols4, int r, bool wants_q) { return cols4 == 256 * r && (wants_q || BITS == 8); }
 template <int BITS> constexpr bool kGroupsFast = BITS < 8;
 template <int BITS> constexpr int kGroupsU = BITS == 8 ? 2 : 1;
 template <int BITS> constexpr int kGroupsCL = 2;
 
 inline bool wants_packed(const RequantArgs& a) { return a.packed != nullptr; }
 inline bool wants_packed(const RequantInlineArgs& a) { return a.packed.p[0] != nullptr; }
+inline bool wants_q(const RequantArgs& a) { return a.q != nullptr; }
+inline bool wants_q(const RequantInlineArgs& a) { return a.q.p[0] != nullptr; }
 
 template <int BITS, bool BATCHED, typename ARGS>
 int32_t launch_bits(const ARGS& a, int count, bool aligned16, hipStream_t st) {
@@ -69,13 +84,21 @@ int32_t launch_bits(const ARGS& a, int count, bool aligned16, hipStream_t st) {
   hipLaunchKernelGGL((requant_rows_kernel<BITS, TPR, R, false, BATCHED, kRowsNT, ARGS>),                      \
                      dim3(static_cast<unsigned>((rows + (256 / TPR) - 1) / (256 / TPR)), gy), \
                      blk, 0, st, a)
+#define MI355Q_ROWS_WIDE(R)                                                                                    \
+  hipLaunchKernelGGL((requant_rows_wide_kernel<BITS, R, false, BATCHED, kRowsNT, kRowsWideNTStores, ARGS>), \
+                     dim3(static_cast<unsigned>(rows), gy), blk, 0, st, a)
+      const bool wq = wants_q(a);
       if (cols4 <= 64) MI355Q_ROWS(64, 1);
       else if (cols4 <= 128) MI355Q_ROWS(64, 2);
       else if (cols4 <= 256) MI355Q_ROWS(64, 4);
       else if (cols4 <= 512) MI355Q_ROWS(256, 2);
+      else if (rows_wide<BITS>(cols4, 4, wq)) MI355Q_ROWS_WIDE(4);
       else if (cols4 <= 1024) MI355Q_ROWS(256, 4);
+      else if (rows_wide<BITS>(cols4, 8, wq)) MI355Q_ROWS_WIDE(8);
       else if (cols4 <= 2048) MI355Q_ROWS(256, 8);
+      else if (rows_wide<BITS>(cols4, 16, wq)) MI355Q_ROWS_WIDE(16);
       else MI355Q_ROWS(256, 16);
+#undef MI355Q_ROWS_WIDE
 #undef MI355Q_ROWS
     } else {
       if (wants_packed(a) && BITS != 8)
@@ -114,8 +137,9 @@ int32_t check_shape(int64_t rows, int64_t cols, int32_t block, int32_t bits,
 
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// The widest store a vector kernel issues to q (packed: the same scaled by bits / 8): the rows kernels emit one float4
-// at a time (a dword of int8, 16 bits of int4, a byte of int2), the groups kernels two (CL = 2). 1 where launch_bits()
+// The widest store a vector kernel needs to issue to q (packed: the same scaled by bits / 8): the rows kernels emit one
+// float4 at a time (a dword of int8, 16 bits of int4, a byte of int2; requant_rows_wide_kernel takes its 16-byte stores
+// only for a tensor whose pointer allows them and these otherwise), the groups kernels two (CL = 2). 1 where launch_bits()
 // takes the generic kernel, which stores bytes. Equally shaped slices of one 16-byte aligned allocation always comply.
 inline unsigned out_align(int64_t cols, int32_t block, int32_t bits, bool packed) {
   const bool vec = cols % 4 == 0 && (block > 0 ? (block == 32 || block == 64 || block == 128 || block == 256)

@@ -3,6 +3,8 @@
 // See requant.hip for the design notes.
 #pragma once
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace mi355q {
@@ -313,6 +315,154 @@ __global__ __launch_bounds__(256) void requant_rows_kernel(ARGS a) {
   for (int j = 0; j < R; ++j) {
     const int c = j * TPR + lane;
     if (c < cols4) emit<BITS, 1, FAST, NT>(v[j], s, row4 + c, q, packed);
+  }
+}
+
+// ------------------------------------------------------------------------
+// (B') one scale per row, for rows that fill rows<256, R> exactly (cols4 == 256 R, R >= 4): the int8 words
+// leave as 16-byte stores. Wave w owns the contiguous run [w 64 R, (w + 1) 64 R) of the row and loads it at
+// run + j 64 + lane (every load instruction 1 KiB contiguous, as in (B)); the words of an output go through a
+// wave-private LDS slab and come back so that every store instruction of the wave writes 1 KiB contiguous.
+// tools/kbench times it against (B) and against the variants it did not take (tools/kbench/rows_variants.h).
+// ------------------------------------------------------------------------
+// Every buffer is global memory, and the accesses of this kernel say so in the pointer type: a buffer pointer
+// read from a device table is a generic pointer to the compiler, and in a kernel that also moves data through
+// LDS it would otherwise become flat_ instructions (counted on both memory counters) instead of global_ ones.
+#define MI355Q_GLOBAL __attribute__((address_space(1)))
+typedef __attribute__((address_space(3))) uint32_t lds_u32;   // LDS stated in the type: no generic pointer to it
+
+template <bool NT>
+__device__ __forceinline__ float4 gload4(const float4* p) {
+  const MI355Q_GLOBAL f32x4_t* g = (const MI355Q_GLOBAL f32x4_t*)p;
+  const f32x4_t v = NT ? __builtin_nontemporal_load(g) : *g;
+  return make_float4(v.x, v.y, v.z, v.w);
+}
+template <bool NT>
+__device__ __forceinline__ void gstore4(uint8_t* p, u32x4_t v) {
+  MI355Q_GLOBAL u32x4_t* g = (MI355Q_GLOBAL u32x4_t*)p;
+  if constexpr (NT) __builtin_nontemporal_store(v, g); else *g = v;
+}
+
+// One float4 of input gives one container word per output: 4 bytes of int8 q, 2 bytes of packed int4, 1 byte of
+// packed int2. store_word: the store (B) uses for it.
+template <int WB> struct WordOf;
+template <> struct WordOf<4> { using type = uint32_t; };
+template <> struct WordOf<2> { using type = uint16_t; };
+template <> struct WordOf<1> { using type = uint8_t; };
+
+template <int WB, bool NT>
+__device__ __forceinline__ void store_word(uint8_t* dst, uint32_t w) {
+  if constexpr (WB == 4) {
+    MI355Q_GLOBAL uint32_t* g = (MI355Q_GLOBAL uint32_t*)dst;
+    if constexpr (NT) __builtin_nontemporal_store(w, g); else *g = w;
+  } else if constexpr (WB == 2) {
+    *(MI355Q_GLOBAL uint16_t*)dst = static_cast<uint16_t>(w);
+  } else {
+    *(MI355Q_GLOBAL uint8_t*)dst = static_cast<uint8_t>(w);
+  }
+}
+
+template <int BITS, bool FAST>
+__device__ __forceinline__ void quant_words(float4 v, float s, float r, uint32_t* w8, uint32_t* subw) {
+  const Quant4<BITS> o = quant4<BITS, FAST>(v, s, r);
+  *w8 = pack_i8<BITS>(o);
+  *subw = pack_sub<BITS>(o);
+}
+
+// Orders the LDS traffic of ONE wave: a wave's LDS instructions execute in program order, so no counter has to
+// drain and no other wave is waited for; the fences only keep the compiler from moving slab accesses across.
+__device__ __forceinline__ void wave_lds_order() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// A wave holds the 64 R words of its run, word j * 64 + lane in lane's w[j]. They are written to the slab at
+// j * 64 + lane (conflict-free) and read back as 16-byte pieces: piece k of lane L is the bytes
+// [(k * 64 + L) * 16, + 16) of the run (for R * WB == 16 lane L holds the R consecutive words [L R, L R + R)).
+// `dst`, the first byte of the run, is 16-byte aligned.
+template <int WB, int R, bool NT>
+__device__ __forceinline__ void exchange_store(lds_u32* slab32, const uint32_t (&w)[R], uint8_t* dst, int lane) {
+  static_assert(R * WB % 16 == 0, "whole 16-byte pieces");
+  using W = typename WordOf<WB>::type;
+  typedef __attribute__((address_space(3))) W lds_w;
+  typedef __attribute__((address_space(3))) u32x4_t lds_u32x4;
+  lds_w* slab = (lds_w*)slab32;
+#pragma unroll
+  for (int j = 0; j < R; ++j) slab[j * kWave + lane] = static_cast<W>(w[j]);
+  wave_lds_order();
+#pragma unroll
+  for (int k = 0; k < R * WB / 16; ++k) {
+    const int o = (k * kWave + lane) * 16;   // byte offset of the piece in the run
+    gstore4<NT>(dst + o, *(lds_u32x4*)((__attribute__((address_space(3))) uint8_t*)slab32 + o));
+  }
+  wave_lds_order();   // the next exchange reuses the slab
+}
+
+// May every 16-byte piece of every row of the output at `p` leave as one store? The pointer and the row pitch
+// decide; both are the same for the whole workgroup, so the branch on it is scalar.
+__device__ __forceinline__ bool wide_ok(const void* p, int64_t row_bytes) {
+  return ((reinterpret_cast<uintptr_t>(p) | static_cast<uintptr_t>(row_bytes)) & 15u) == 0;
+}
+
+// The wide stores are taken per tensor and per output, where the output pointer is 16-byte aligned (the batched
+// forms promise no more than out_align() of requant.hip; the row pitch is a multiple of 1 KiB here); a packed
+// sub-byte output takes them where a lane holds 16 bytes of it (int4: R >= 8, int2: R = 16). Every other output
+// leaves as in (B), a word per store. NT: non-temporal loads and word stores; NTS: non-temporal 16-byte stores.
+template <int BITS, int R, bool FAST, bool BATCHED, bool NT, bool NTS, typename ARGS = RequantArgs>
+__global__ __launch_bounds__(256) void requant_rows_wide_kernel(ARGS a) {
+  static_assert(R >= 4 && R % 4 == 0, "a lane holds whole 16-byte pieces of q");
+  const int t = BATCHED ? blockIdx.y : 0;
+  const float4* __restrict__ x = pick<BATCHED, const float4>(a.x, t);
+  int8_t* q = pick<BATCHED, int8_t>(a.q, t);
+  uint8_t* packed = pick<BATCHED, uint8_t>(a.packed, t);
+  float* scale = pick<BATCHED, float>(a.scale, t);
+  const float* clip = BATCHED ? nullptr : a.clip;
+
+  const int64_t row = blockIdx.x;           // a.cols == 1024 R: the host launches this kernel for no other width
+  const int64_t row4 = row * (256 * R);
+  const int lane = threadIdx.x & (kWave - 1);
+  const int run = (threadIdx.x / kWave) * (kWave * R);
+
+  float4 v[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) v[j] = gload4<NT>(x + row4 + run + j * kWave + lane);
+  uint32_t m = 0;
+#pragma unroll
+  for (int j = 0; j < R; ++j) m = max(m, absmax4(v[j]));
+  m = group_max_u32<kWave>(m);
+  __shared__ uint32_t part[256 / kWave];
+  if (lane == 0) part[threadIdx.x / kWave] = m;
+  __syncthreads();
+  m = max(max(part[0], part[1]), max(part[2], part[3]));
+  uint16_t hb;
+  const float s = make_scale<BITS, false>(m, clip, row, &hb);
+  if (threadIdx.x == 0) *(MI355Q_GLOBAL float*)(scale + row) = s;
+
+  constexpr int SUBB = BITS / 2;   // bytes of packed output per float4 (4, 2, 1)
+  if (BITS == 8 && reinterpret_cast<int8_t*>(packed) == q) packed = nullptr;   // the same bytes: written once
+  __shared__ __attribute__((aligned(16))) uint32_t slabs[256 / kWave][kWave * R];
+  lds_u32* slab = (lds_u32*)slabs[threadIdx.x / kWave];
+  const float r = FAST ? 1.0f / s : 0.f;
+  uint32_t w8[R], subw[R];
+#pragma unroll
+  for (int j = 0; j < R; ++j) quant_words<BITS, FAST>(v[j], s, r, &w8[j], &subw[j]);
+  auto out = [&](auto wb, const uint32_t (&w)[R], uint8_t* base) {
+    constexpr int WB = decltype(wb)::value;
+    uint8_t* dst = base + (row4 + run) * WB;   // the wave's run
+    if constexpr (R * WB % 16 == 0) {
+      if (wide_ok(base, a.cols / 4 * WB)) {
+        exchange_store<WB, R, NTS>(slab, w, dst, lane);
+        return;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < R; ++j) store_word<WB, NT>(dst + (j * kWave + lane) * WB, w[j]);
+  };
+  if (q != nullptr) out(std::integral_constant<int, 4>{}, w8, reinterpret_cast<uint8_t*>(q));
+  if (packed != nullptr) {
+    if constexpr (BITS == 8) out(std::integral_constant<int, 4>{}, w8, packed);
+    else out(std::integral_constant<int, SUBB>{}, subw, packed);
   }
 }
 

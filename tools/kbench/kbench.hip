@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "requant_kernels.h"
+#include "rows_variants.h"
 
 namespace mi355q {  // the kernels reference these; no host error plumbing needed here
 void set_error(const char*, ...) {}
@@ -73,25 +74,25 @@ struct Case {
   const char* name;
   int64_t rows, cols; int block, bits, pool; bool packed_only;
   std::vector<Buf> bufs;
-  void** tx; void** tq; void** tp; void** ts; void** t16;
+  void** tx; void** tq; void** tq8; void** tp; void** ts; void** t16;   // tq8: every q + 8 bytes
   size_t alg_bytes;
 };
 
 static void alloc_case(Case& c, float sigma, int mode) {
   size_t n = (size_t)c.rows * c.cols;
   size_t nscale = c.block ? n / c.block : c.rows;
-  std::vector<void*> hx, hq, hp, hs, h16;
+  std::vector<void*> hx, hq, hq8, hp, hs, h16;
   for (int i = 0; i < c.pool; ++i) {
     Buf b{};
-    CK(hipMalloc(&b.x, n * 4)); CK(hipMalloc(&b.q, n)); CK(hipMalloc(&b.p, n)); CK(hipMalloc(&b.s, nscale * 4));
+    CK(hipMalloc(&b.x, n * 4)); CK(hipMalloc(&b.q, n + 16)); CK(hipMalloc(&b.p, n)); CK(hipMalloc(&b.s, nscale * 4));
     CK(hipMalloc(&b.s16, nscale * 2));
     fill_kernel<<<4096, 256>>>(b.x, n, 1234u + i, sigma, mode);
     if (mode == 1) pin_rowmax_kernel<<<(c.rows + 255) / 256, 256>>>(b.x, (int)c.rows, (int)c.cols, 4.0f);
     c.bufs.push_back(b);
-    hx.push_back(b.x); hq.push_back(b.q); hp.push_back(b.p); hs.push_back(b.s); h16.push_back(b.s16);
+    hx.push_back(b.x); hq.push_back(b.q); hq8.push_back(b.q + 8); hp.push_back(b.p); hs.push_back(b.s); h16.push_back(b.s16);
   }
   auto up = [&](std::vector<void*>& h, void**& d) { CK(hipMalloc(&d, h.size() * sizeof(void*))); CK(hipMemcpy(d, h.data(), h.size() * sizeof(void*), hipMemcpyHostToDevice)); };
-  up(hx, c.tx); up(hq, c.tq); up(hp, c.tp); up(hs, c.ts); up(h16, c.t16);
+  up(hx, c.tx); up(hq, c.tq); up(hq8, c.tq8); up(hp, c.tp); up(hs, c.ts); up(h16, c.t16);
   CK(hipDeviceSynchronize());
 }
 
@@ -107,12 +108,12 @@ static float time_ms(F launch, int iters) {
   return ms / iters;
 }
 
-static std::vector<uint8_t> snapshot(const Case& c, bool packed) {
+static std::vector<uint8_t> snapshot(const Case& c, bool packed, bool plus8 = false) {
   size_t n = (size_t)c.rows * c.cols;
   size_t nb = packed ? n * c.bits / 8 : n;
   size_t nscale = c.block ? n / c.block : c.rows;
   std::vector<uint8_t> h(nb + nscale * 4);
-  CK(hipMemcpy(h.data(), packed ? (void*)c.bufs[1].p : (void*)c.bufs[1].q, nb, hipMemcpyDeviceToHost));
+  CK(hipMemcpy(h.data(), packed ? (void*)c.bufs[1].p : (void*)(c.bufs[1].q + (plus8 ? 8 : 0)), nb, hipMemcpyDeviceToHost));
   CK(hipMemcpy(h.data() + nb, c.bufs[1].s, nscale * 4, hipMemcpyDeviceToHost));
   return h;
 }
@@ -125,13 +126,14 @@ struct Variant {
   bool packed;
   std::vector<float> ms;
   std::string verdict;
+  bool plus8 = false;   // q at + 8 bytes
 };
 
 static void run_interleaved(const Case& c, std::vector<Variant>& vs, int rounds, int iters) {
   for (size_t k = 0; k < vs.size(); ++k) {  // correctness first
     vs[k].launch();
     CK(hipDeviceSynchronize());
-    auto snap = snapshot(c, vs[k].packed);
+    auto snap = snapshot(c, vs[k].packed, vs[k].plus8);
     if (k == 0) { g_ref = snap; vs[k].verdict = "ref"; }
     else vs[k].verdict = (snap == g_ref) ? "bit-exact" : "MISMATCH";
   }
@@ -148,11 +150,71 @@ static void run_interleaved(const Case& c, std::vector<Variant>& vs, int rounds,
 }
 
 template <int BITS, int TPR, int R, bool FAST, bool NT = false>
-static Variant rows_variant(Case& c, const char* tag) {
+static Variant rows_variant(Case& c, const char* tag, bool plus8 = false) {
+  RequantArgs a{c.tx, plus8 ? c.tq8 : c.tq, nullptr, c.ts, nullptr, nullptr, c.rows, c.cols, 0};
+  if (c.packed_only) { a.q = nullptr; a.packed = c.tp; }
+  dim3 grid((unsigned)((c.rows + (256 / TPR) - 1) / (256 / TPR)), c.pool);
+  return Variant{tag, [=] { hipLaunchKernelGGL((requant_rows_kernel<BITS, TPR, R, FAST, true, NT>), grid, dim3(256), 0, 0, a); }, c.packed_only, {}, "", plus8};
+}
+
+// The store variants the library does not use (rows_variants.h: WIDE = 1 pairs, WIDE = 2 the exchange at any width).
+template <int BITS, int TPR, int R, int WIDE, bool NTS>
+static Variant rows_store_variant(Case& c, const char* tag) {
   RequantArgs a{c.tx, c.tq, nullptr, c.ts, nullptr, nullptr, c.rows, c.cols, 0};
   if (c.packed_only) { a.q = nullptr; a.packed = c.tp; }
   dim3 grid((unsigned)((c.rows + (256 / TPR) - 1) / (256 / TPR)), c.pool);
-  return Variant{tag, [=] { hipLaunchKernelGGL((requant_rows_kernel<BITS, TPR, R, FAST, true, NT>), grid, dim3(256), 0, 0, a); }, c.packed_only, {}, ""};
+  return Variant{tag, [=] { hipLaunchKernelGGL((rows_variants_kernel<BITS, TPR, R, false, true, true, RequantArgs, WIDE, NTS>), grid, dim3(256), 0, 0, a); }, c.packed_only, {}, "", false};
+}
+
+// The library's kernel for rows that fill rows<256, R> exactly; plus8: every q 8 bytes past a 16-byte boundary,
+// where it falls back to a word per store.
+template <int BITS, int R, bool NTS>
+static Variant rows_wide_variant(Case& c, const char* tag, bool plus8 = false) {
+  RequantArgs a{c.tx, plus8 ? c.tq8 : c.tq, nullptr, c.ts, nullptr, nullptr, c.rows, c.cols, 0};
+  if (c.packed_only) { a.q = nullptr; a.packed = c.tp; }
+  dim3 grid((unsigned)c.rows, c.pool);
+  return Variant{tag, [=] { hipLaunchKernelGGL((requant_rows_wide_kernel<BITS, R, false, true, true, NTS>), grid, dim3(256), 0, 0, a); }, c.packed_only, {}, "", plus8};
+}
+
+// Loads are non-temporal in all of them; "word stores nt" is the library's rows kernel (B).
+template <int BITS, int TPR, int R>
+static void rows_store_variants(Case& c, int rounds, int iters) {
+  std::vector<Variant> vs;
+  vs.push_back(rows_variant<BITS, TPR, R, false, true>(c, "rows word stores nt"));
+  vs.push_back(rows_store_variant<BITS, TPR, R, 1, true>(c, "rows A pairs nt"));
+  vs.push_back(rows_store_variant<BITS, TPR, R, 1, false>(c, "rows A pairs plain st"));
+  vs.push_back(rows_store_variant<BITS, TPR, R, 2, true>(c, "rows B exchange nt"));
+  vs.push_back(rows_store_variant<BITS, TPR, R, 2, false>(c, "rows B exchange plain st"));
+  if constexpr (TPR == 256 && R >= 4) {
+    if (c.cols == 1024 * R) {
+      vs.push_back(rows_wide_variant<BITS, R, true>(c, "rows wide kernel nt"));
+      vs.push_back(rows_wide_variant<BITS, R, false>(c, "rows wide kernel plain st"));
+    }
+  }
+  run_interleaved(c, vs, rounds, iters);
+  if constexpr (TPR == 256 && R >= 4) {
+    if (c.cols == 1024 * R && !c.packed_only) {   // the fall-back of a tensor whose q is only 8-byte aligned
+      std::vector<Variant> v8;
+      v8.push_back(rows_variant<BITS, TPR, R, false, true>(c, "rows word stores nt, q + 8", true));
+      v8.push_back(rows_wide_variant<BITS, R, false>(c, "rows wide kernel, q + 8", true));
+      run_interleaved(c, v8, rounds, iters);
+    }
+  }
+}
+
+// One row width: int8 q, then int4 packed alone, on the same buffers.
+template <int TPR, int R>
+static void rows_store_case(const char* name8, const char* name4, int64_t cols, int pool, int mode, int rounds) {
+  Case c{name8, 4096, cols, 0, 8, pool, false};
+  c.alg_bytes = 4096ull * cols * 5 + 4096 * 4 + 4096;
+  alloc_case(c, 1.0f, mode);
+  rows_store_variants<8, TPR, R>(c, rounds, 30);
+  Case c4{name4, 4096, cols, 0, 4, pool, true};
+  c4.alg_bytes = 4096ull * cols * 4 + 4096ull * cols / 2 + 4096 * 4;
+  c4.bufs = c.bufs; c4.tx = c.tx; c4.tq = c.tq; c4.tq8 = c.tq8; c4.tp = c.tp; c4.ts = c.ts; c4.t16 = c.t16;
+  rows_store_variants<4, TPR, R>(c4, rounds, 30);
+  for (auto& b : c.bufs) { hipFree(b.x); hipFree(b.q); hipFree(b.p); hipFree(b.s); hipFree(b.s16); }
+  for (void** t : {c.tx, c.tq, c.tq8, c.tp, c.ts, c.t16}) hipFree(t);
 }
 
 template <int BITS, int G4, int U, int CL, bool FAST, bool NT = false>
@@ -166,10 +228,19 @@ static Variant groups_variant(Case& c, const char* tag) {
 
 int main(int argc, char** argv) {
   int mode = argc > 1 ? atoi(argv[1]) : 0;  // 1 = adversarial half-integer data
+  const bool only_rows_stores = argc > 2 && strcmp(argv[2], "rows-stores") == 0;   // skip the older sections
   hipDeviceProp_t prop; CK(hipGetDeviceProperties(&prop, 0));
   printf("# device %s, %d CUs; data mode %d\n", prop.gcnArchName, prop.multiProcessorCount, mode);
 
   const int rounds = 7;
+  {  // ---- rows kernel store variants: C2 and the other row widths of a Llama / Gemma layer (1 GiB in each)
+    rows_store_case<256, 4>("C2 4096x4096 cw int8", "C2 4096x4096 cw int4 packed", 4096, 16, mode, rounds);
+    rows_store_case<256, 4>("4096x3072 cw int8", "4096x3072 cw int4 packed", 3072, 21, mode, rounds);
+    rows_store_case<256, 8>("4096x8192 cw int8", "4096x8192 cw int4 packed", 8192, 8, mode, rounds);
+    rows_store_case<256, 16>("4096x11008 cw int8", "4096x11008 cw int4 packed", 11008, 6, mode, rounds);
+    rows_store_case<256, 16>("4096x16384 cw int8", "4096x16384 cw int4 packed", 16384, 4, mode, rounds);
+  }
+  if (only_rows_stores) return 0;
   {  // ---- C2: 4096x4096 per-channel int8, pool of 16 (1 GiB in)
     Case c{"C2 4096x4096 cw int8", 4096, 4096, 0, 8, 16, false};
     c.alg_bytes = 4096ull * 4096 * 5 + 4096 * 4 + 4096;
