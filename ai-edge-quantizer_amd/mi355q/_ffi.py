@@ -127,6 +127,8 @@ PROTOTYPES = {
                                    c_size, c_ptr]),
     "mi355q_compare_f32_batched": (c_i32, [c_ptr, c_i32, c_i64, c_i32, c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_weight_delta_f32": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_i32, c_i64, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mi355q_weight_delta_transformed_f32": (c_i32, [c_ptr, c_ptr, c_i64, c_i32, c_i32, c_i64, c_i64, c_ptr, c_ptr,
+                                                    c_i64, c_ptr, c_i32, c_ptr, c_ptr]),
     "mi355q_quadform_rows_workspace_bytes": (c_size, [c_i64, c_i64]),
     "mi355q_quadform_rows_f32": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_f64, c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_clock_probe": (c_i32, [c_f64, c_ptr, c_ptr]),

@@ -19,6 +19,8 @@ from typing import Any, Optional, Union
 import numpy as np
 
 from . import schema
+from .transformations import graph_edits
+from .utils import flexbuffer
 from .utils import tfl_flatbuffer_utils
 from .utils import validation_utils
 
@@ -519,8 +521,113 @@ def layer_hessians(float_model, samples: Iterable[dict], signature_key: Optional
   return out
 
 
+_MUL, _RESHAPE, _CUSTOM = 18, 22, 32
+_HADAMARD_CUSTOM_CODE = "aeq.hadamard_rotation"
+_MAX_HADAMARD_SIZE = 16384
+TRANSFORM_NONE, TRANSFORM_MULTIPLY, TRANSFORM_HADAMARD = "none", "multiply", "hadamard"
+
+
+def _producers(sg) -> dict:
+  """tensor index -> the op that writes it."""
+  producers: dict[int, Any] = {}
+  for op in sg.operators or []:
+    for o in op.outputs:
+      producers.setdefault(int(o), op)
+  return producers
+
+
+def _input_transform(m, sg, producers: dict, fc_op, x_name: str, d: int) -> Optional[tuple]:
+  """(kind, multiplier or None, hadamard size) of the linear map between the float model's activation `x_name` and
+  input 0 of the target FULLY_CONNECTED op `fc_op`, or None when its producer is none of the three inserted shapes:
+  MUL(x, constant float32 [d]) (OSCAR), CUSTOM aeq.hadamard_rotation(x) with a vector of ones, and
+  RESHAPE <- FULLY_CONNECTED(., H_h / sqrt(h)) <- RESHAPE(x) with exactly graph_edits' float32 matrix, the first
+  RESHAPE to [-1, h] and the second back to x's shape. A fused activation or a bias on the MUL or on the rotation's
+  FULLY_CONNECTED would make it another map: refused."""
+  def plain(op) -> bool:
+    """No fused activation function."""
+    return int(getattr(op.builtinOptions, "fusedActivationFunction", 0) or 0) == 0
+
+  def shape(index) -> Optional[list]:
+    t = sg.tensors[index] if index >= 0 else None
+    return None if t is None or t.shape is None else [int(v) for v in t.shape]
+
+  def code(op) -> int:
+    return int(m.operatorCodes[op.opcodeIndex].builtinCode)
+
+  def name(index) -> Optional[str]:
+    return schema.tensor_name(sg.tensors[index]) if index is not None and index >= 0 else None
+
+  def constant_f32(index, count) -> Optional[np.ndarray]:
+    if index < 0:
+      return None
+    t = sg.tensors[index]
+    if t.type != schema.TensorType.FLOAT32 or not _has_data(m.buffers, t) or _numel(t) != count:
+      return None
+    return np.ascontiguousarray(_raw_bytes(m.buffers, t)).view(np.float32)[:count]
+
+  def rotation(h: int) -> Optional[tuple]:
+    if h < 1 or h & (h - 1) or h > _MAX_HADAMARD_SIZE or d % h:
+      return None
+    return (TRANSFORM_NONE, None, 0) if h == 1 else (TRANSFORM_HADAMARD, None, h)
+
+  if code(fc_op) != _FULLY_CONNECTED or not len(fc_op.inputs) or fc_op.inputs[0] < 0:
+    return None
+  op = producers.get(int(fc_op.inputs[0]))
+  if op is None:
+    return None
+  kind = code(op)
+  if kind == _MUL and len(op.inputs) == 2 and plain(op):
+    for a, b in ((0, 1), (1, 0)):
+      if name(op.inputs[a]) == x_name:
+        multiplier = constant_f32(int(op.inputs[b]), d)
+        if multiplier is not None:
+          return TRANSFORM_MULTIPLY, multiplier, 0
+    return None
+  if kind == _CUSTOM:
+    custom = m.operatorCodes[op.opcodeIndex].customCode
+    custom = custom.decode() if isinstance(custom, (bytes, bytearray)) else custom
+    if custom != _HADAMARD_CUSTOM_CODE or not len(op.inputs) or name(op.inputs[0]) != x_name:
+      return None
+    try:
+      options = flexbuffer.decode(bytes(bytearray(op.customOptions)))
+      h = int(options["hadamard_size"])
+      signs = list(options["random_binary_vector"])
+    except (ValueError, KeyError, TypeError, IndexError):
+      return None
+    if len(signs) != h or any(v != 1 for v in signs):      # (the reference emits ones only: another vector, another map)
+      return None
+    return rotation(h)
+  if kind == _RESHAPE and len(op.inputs):
+    fc = producers.get(int(op.inputs[0]))
+    if fc is None or code(fc) != _FULLY_CONNECTED or len(fc.inputs) < 2 or not plain(fc):
+      return None
+    if len(fc.inputs) > 2 and fc.inputs[2] >= 0:      # a bias
+      return None
+    pre = producers.get(int(fc.inputs[0]))
+    if pre is None or code(pre) != _RESHAPE or not len(pre.inputs) or name(pre.inputs[0]) != x_name:
+      return None
+    matrix = sg.tensors[fc.inputs[1]] if fc.inputs[1] >= 0 else None
+    if matrix is None or matrix.shape is None or len(matrix.shape) != 2 or matrix.shape[0] != matrix.shape[1]:
+      return None
+    h = int(matrix.shape[0])
+    found = rotation(h)
+    values = constant_f32(int(fc.inputs[1]), h * h)
+    if found is None or values is None:
+      return None
+    x_shape, flat = shape(int(pre.inputs[0])), shape(int(fc.inputs[0]))
+    if x_shape is None or flat is None or len(flat) != 2 or flat[1] != h or shape(int(fc.outputs[0])) != flat:
+      return None
+    if flat[0] * h != int(np.prod(x_shape)) or shape(int(op.outputs[0])) != x_shape or x_shape[-1] != d:
+      return None
+    want = graph_edits._sylvester_hadamard_f32(h)      # pylint: disable=protected-access
+    if not np.array_equal(values.view(np.uint32), want.reshape(-1).view(np.uint32)):
+      return None
+    return found
+  return None
+
+
 class LayerErrorKernels:
-  """The device side of compare_layer_outputs: where the operands live and the two kernels."""
+  """The device side of compare_layer_outputs: where the operands live and the kernels."""
 
   def weight(self, values: np.ndarray):
     from . import runtime as rt
@@ -529,6 +636,15 @@ class LayerErrorKernels:
   def delta(self, reference, plan: ConstantPlan):
     from . import ops
     return ops.weight_delta(reference, _device_target(plan))
+
+  def delta_transformed(self, reference, plan: ConstantPlan, d: int, multiplier, hadamard_size: int):
+    """The delta of a weight stored in a transformed basis (ops.weight_delta_transformed): `multiplier` is the
+    float32 [d] constant of an inserted MUL or None, `hadamard_size` the size of an inserted rotation or 0. Called
+    only when compare_layer_outputs found such a transformation."""
+    from . import ops
+    from . import runtime as rt
+    m = None if multiplier is None else rt.to_device(np.asarray(multiplier, np.float32))
+    return ops.weight_delta_transformed(reference, _device_target(plan), d, m, hadamard_size)
 
   def hessian(self, stat):
     """(float32 [d, d] whose lower triangle is valid, alpha) with H = alpha * product."""
@@ -548,8 +664,8 @@ class LayerErrorKernels:
 class LayerOutputComparison:
   """Per FULLY_CONNECTED op (keyed by its output tensor's name): how far the quantized weight moves the op's
   output over the calibration set. `results[name]` holds `weight`, `input`, `rows`, `d`, `signal`, `error`,
-  `output_mse`, `output_snr` and `per_channel_error` (float64 [rows]); `skipped[name]` is the reason an op was
-  not computed."""
+  `output_mse`, `output_snr` and `per_channel_error` (float64 [rows]), with `follow_input_transforms` also
+  `input_transform` and `hadamard_size`; `skipped[name]` is the reason an op was not computed."""
 
   def __init__(self, signature_key: Optional[str] = None):
     self.signature_key = signature_key
@@ -584,7 +700,8 @@ class LayerOutputComparison:
 
 def compare_layer_outputs(reference_model, target_model, calibration_result: dict,
                           signature_key: Optional[str] = DEFAULT_SIGNATURE_KEY, *,
-                          kernels: Optional[LayerErrorKernels] = None) -> LayerOutputComparison:
+                          kernels: Optional[LayerErrorKernels] = None,
+                          follow_input_transforms: bool = False) -> LayerOutputComparison:
   """Output error of every FULLY_CONNECTED op of the float model with a constant 2-D weight [rows, d].
 
   With H = calibration_result[input 0's name]["hessian"] = (2/n) X^T X and dW = W - dequant(W^), the target weight
@@ -595,9 +712,18 @@ def compare_layer_outputs(reference_model, target_model, calibration_result: dic
   tokens, and a saved calibration result serves as well as a fresh one.
 
   This is the weight's contribution to the op's pre-activation output: bias and fused activation do not enter, and
-  under static recipes the activations' own rounding is not included. Ops whose quantized form reads a transformed
-  activation (an inserted Hadamard rotation or OSCAR multiply) are reported in `.skipped`, not computed: their
-  stored weight lives in the transformed basis. Non-finite Hessians give non-finite results, which is no error.
+  under static recipes the activations' own rounding is not included. Non-finite Hessians give non-finite results,
+  which is no error.
+
+  Ops whose quantized form reads a transformed activation (an inserted Hadamard rotation or OSCAR multiply) store
+  their weight in the transformed basis and are reported in `.skipped` unless `follow_input_transforms` is set. Then
+  the producer of the target op's input is looked at (_input_transform): both transformations are linear maps on the
+  reduction dimension whose constants are in the quantized graph, y = (x * m) W^'T = x (W^ diag(m))^T and
+  y = (x R) W^'T = x (W^ R)^T with R = blockdiag(H_h / sqrt(h)) symmetric, so the error is the same form against the
+  same Hessian of the UNTRANSFORMED input with dW = W - dequant(W^) * m, or dW = W - rotate_h(dequant(W^))
+  (kernels.delta_transformed). Every entry then also carries `input_transform` ("none", "multiply" or "hadamard")
+  and `hadamard_size` (0 when none). A chain of two transformations, a rotation with another sign vector or matrix,
+  or any other producer stays in `.skipped`.
   """
   kernels = kernels or LayerErrorKernels()
   ref, tgt = _as_model(reference_model), _as_model(target_model)
@@ -608,10 +734,13 @@ def compare_layer_outputs(reference_model, target_model, calibration_result: dic
   for t in tgt_sg.tensors:
     by_name.setdefault(schema.tensor_name(t), t)
   producer_input: dict[str, Optional[str]] = {}     # output tensor name -> name of its producer's input 0
+  producer_op: dict[str, Any] = {}
+  producers = _producers(tgt_sg) if follow_input_transforms else {}
   for op in tgt_sg.operators or []:
     first = schema.tensor_name(tgt_sg.tensors[op.inputs[0]]) if len(op.inputs) and op.inputs[0] >= 0 else None
     for o in op.outputs:
       producer_input.setdefault(schema.tensor_name(tgt_sg.tensors[o]), first)
+      producer_op.setdefault(schema.tensor_name(tgt_sg.tensors[o]), op)
   out = LayerOutputComparison(signature_key)
   hessians: dict[str, tuple] = {}
   signals: dict[tuple, np.ndarray] = {}             # (weight name, input name) -> per-row signal
@@ -633,9 +762,15 @@ def compare_layer_outputs(reference_model, target_model, calibration_result: dic
     if target is None or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
       out.skipped[y_name] = SKIP_TARGET
       continue
+    transform = (TRANSFORM_NONE, None, 0)
     if producer_input.get(y_name) != x_name:
-      out.skipped[y_name] = SKIP_INPUT
-      continue
+      found = None
+      if follow_input_transforms and y_name in producer_op:
+        found = _input_transform(tgt, tgt_sg, producers, producer_op[y_name], x_name, d)
+      if found is None:
+        out.skipped[y_name] = SKIP_INPUT
+        continue
+      transform = found
     values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
     plan = _target_plan(w_name, values, tgt, target)
     if plan is None:
@@ -652,10 +787,16 @@ def compare_layer_outputs(reference_model, target_model, calibration_result: dic
     if (w_name, x_name) not in signals:
       signals[(w_name, x_name)] = kernels.quadform(w_dev, rows, d, product, 0.5 * alpha)
     per_row_signal = signals[(w_name, x_name)]
-    per_channel = kernels.quadform(kernels.delta(w_dev, plan), rows, d, product, 0.5 * alpha)
+    if transform[0] == TRANSFORM_NONE:
+      delta = kernels.delta(w_dev, plan)
+    else:
+      delta = kernels.delta_transformed(w_dev, plan, d, transform[1], transform[2])
+    per_channel = kernels.quadform(delta, rows, d, product, 0.5 * alpha)
     signal, error = float(np.sum(per_row_signal)), float(np.sum(per_channel))
     mse = error / rows
     out.results[y_name] = {"weight": w_name, "input": x_name, "rows": rows, "d": d, "signal": signal, "error": error,
                            "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
                            "per_channel_error": per_channel}
+    if follow_input_transforms:
+      out.results[y_name].update(input_transform=transform[0], hadamard_size=transform[2])
   return out

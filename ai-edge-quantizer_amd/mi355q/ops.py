@@ -984,6 +984,39 @@ def weight_delta(reference: torch.Tensor, target: CompareTarget) -> torch.Tensor
   return out
 
 
+def weight_delta_transformed(reference: torch.Tensor, target: CompareTarget, d: int,
+                             multiplier: torch.Tensor | None = None, hadamard_size: int = 0) -> torch.Tensor:
+  """float32 [n]: the delta of a [n // d, d] weight whose quantized op reads a transformed activation
+  (mi355q_weight_delta_transformed_f32). With `multiplier` (float32 [d]): reference - dequant(target) * multiplier
+  per column, the product rounded to float32 before the subtraction. With `hadamard_size` h > 1 (a power of two
+  <= 16384 that divides d): reference - hadamard_rotate(dequant(target), h), the butterfly network of
+  `hadamard_rotate` fed from the stored target in one pass. With neither it equals `weight_delta`; both at once is
+  refused. Does not synchronize."""
+  rt.require_gpu()
+  reference = _f32(reference).view(-1)
+  if reference.numel() != target.n:
+    raise ValueError("data1 & data2 must be of the same size")
+  d, h = int(d), int(hadamard_size)
+  if d < 1 or target.n % d:
+    raise ValueError(f"tensor size {target.n} is not a multiple of the row length {d}")
+  if h < 0 or h & (h - 1):
+    raise ValueError("Hadamard matrix size must be a power of 2. ")
+  if h > 1 and (h > 16384 or d % h):
+    raise ValueError(f"Hadamard size {h} must divide the row length {d} and be at most 16384")
+  if multiplier is not None:
+    if h > 1:
+      raise ValueError("a multiplier and a Hadamard rotation at once are not supported")
+    multiplier = _f32(multiplier).view(-1)
+    if multiplier.numel() != d:
+      raise ValueError(f"multiplier has {multiplier.numel()} elements, the row length is {d}")
+  out = rt.empty((target.n,), torch.float32)
+  _ffi.check(_ffi.lib().mi355q_weight_delta_transformed_f32(
+      rt.ptr(reference), rt.ptr(target.data), target.n, COMPARE_KINDS[target.kind], target.diff_bits, target.channels,
+      target.inner, rt.ptr(target.scale), rt.ptr(target.zero_point), d, rt.ptr(multiplier), h, rt.ptr(out),
+      rt.stream_ptr()))
+  return out
+
+
 def quadform_rows(a: torch.Tensor, product: torch.Tensor, alpha: float) -> torch.Tensor:
   """float64 [rows]: alpha * a_r Psym a_r^T for float32 a [rows, d] and the symmetric matrix whose LOWER triangle
   is `product` (float32 [d, d], e.g. HessianAccumulator.product_form(); the upper triangle is never read and

@@ -211,7 +211,8 @@ class Quantizer:
 
   def validate_layer_outputs(self, calibration_result: Optional[dict] = None, calibration_data: Optional[Any] = None,
                              signature_key: Optional[str] = None, save_folder: Optional[str] = None,
-                             model_name: Optional[str] = None) -> model_validator.LayerOutputComparison:
+                             model_name: Optional[str] = None, follow_input_transforms: bool = False
+                             ) -> model_validator.LayerOutputComparison:
     """Output error of every FULLY_CONNECTED op of the last quantize() result over the calibration set:
     error = 1/2 tr(dW H dW^T) = (1/n) ||X dW^T||_F^2 per op, with its signal, MSE, SNR and per-channel errors
     (model_validator.compare_layer_outputs; no run of the model is needed).
@@ -219,6 +220,11 @@ class Quantizer:
     Exactly one of `calibration_result` (what calibrate() returned for a recipe that keeps Hessians, or a loaded
     one) and `calibration_data` (the samples calibrate() takes: a list of {tensor name: array or device tensor}, or
     {signature key: such a list}; their Hessians are formed here) is required.
+
+    Ops behind an inserted Hadamard rotation (custom op or decomposed) or OSCAR multiply are listed in `.skipped`
+    unless `follow_input_transforms` is set: then their stored weight is mapped back through the inserted op's own
+    constant (dW = W - rotate_h(dequant(W^)), or W - dequant(W^) * multiplier) and measured against the Hessian of the
+    float model's untransformed input, and every entry also says which `input_transform` and `hadamard_size` it had.
     """
     quantized_model = self._result.quantized_model
     if quantized_model is None:
@@ -238,7 +244,7 @@ class Quantizer:
           raise ValueError("signature_key is required when calibration_data holds several signatures")
       calibration_result = model_validator.layer_hessians(self.float_model, samples, signature_key)
     results = model_validator.compare_layer_outputs(self.float_model, bytes(quantized_model), calibration_result,
-                                                    signature_key)
+                                                    signature_key, follow_input_transforms=follow_input_transforms)
     if save_folder:
       if model_name is None:
         model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"

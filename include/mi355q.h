@@ -825,10 +825,35 @@ int32_t mi355q_compare_f32_batched(const mi355q_compare_pair* pairs, int32_t cou
  * order. Non-finite inputs give non-finite rows; rows = 0 enqueues nothing.
  * workspace: mi355q_quadform_rows_workspace_bytes(rows, d) =
  * rows * ceil(d / 64) * 8 rounded up to 256 bytes.
+ *
+ * mi355q_weight_delta_transformed_f32 (csrc/hadamard.hip): the delta of a weight
+ * whose quantized op reads a TRANSFORMED activation. Both transformations the
+ * recipes insert are linear maps on the reduction dimension, so the error is the
+ * same quadratic form against the Hessian of the untransformed input with
+ *   multiply   y = (x * m) W^'T:   dW = W - dequant(W^) * m   (m: d floats, column e % d)
+ *   Hadamard   y = (x R) W^'T:     dW = W - rotate_h(dequant(W^)),  R = blockdiag(H_h / sqrt(h))
+ * The target is described as for mi355q_weight_delta_f32; d is the row length
+ * (n % d == 0). `multiplier` may be NULL; hadamard_size 0 or 1 means no rotation,
+ * otherwise it is a power of two <= 16384 that divides d. With neither, the
+ * result is mi355q_weight_delta_f32's bit for bit; both at once is
+ * MI355Q_UNSUPPORTED. Multiply: delta_out[e] = reference[e] - fl(dq[e] * m[e % d]),
+ * the float32 product rounded once, then a float32 subtraction. Hadamard: rotate_h
+ * is the float32 butterfly network of mi355q_hadamard_rotate_f32 for aligned
+ * operands (r = 1 / sqrtf(h) on load; the radix-2 LDS kernel for h < 256, the
+ * radix-16 tiles of 4096 / 8192 / 16384 elements above) instantiated with the
+ * dequantizing load and `reference[e] - v` as its store, so the result equals
+ * dequantize -> mi355q_hadamard_rotate_f32 -> subtract bit for bit without the
+ * two n-element temporaries. The network is chosen from h alone: misaligned
+ * reference / delta_out only make the accesses scalar. delta_out must not alias
+ * the inputs. n = 0 enqueues nothing.
  * ------------------------------------------------------------------------ */
 int32_t mi355q_weight_delta_f32(const float* reference, const void* target, int64_t n, int32_t target_kind,
                                 int32_t diff_bits, int64_t channels, int64_t inner, const float* scale,
                                 const int32_t* zero_point, float* delta_out, void* stream);
+int32_t mi355q_weight_delta_transformed_f32(
+    const float* reference, const void* target, int64_t n, int32_t target_kind, int32_t diff_bits,
+    int64_t channels, int64_t inner, const float* scale, const int32_t* zero_point,
+    int64_t d, const float* multiplier, int32_t hadamard_size, float* delta_out, void* stream);
 size_t mi355q_quadform_rows_workspace_bytes(int64_t rows, int64_t d);
 int32_t mi355q_quadform_rows_f32(const float* a, int64_t rows, int64_t d, const float* product, double alpha,
                                  double* out_rows, void* workspace, size_t workspace_bytes, void* stream);

@@ -9,6 +9,12 @@ d = 16384 product (down). Medians of device-event times; the mirrored matrix is 
 kernel reads half the products and writes no rows x d intermediate, so it must not be slower at either shape
 (`not_slower`). With --model-layers N > 0 one Quantizer.validate_layer_outputs call on the N-layer full-shape model
 of tests/test_gpu_c5_model.py (GPTQ int4) is timed too. One JSON line, also written to --out.
+
+With --transforms the effective-weight delta behind an inserted transformation (ops.weight_delta_transformed, one
+launch) is timed against the three launches the library offered before it -- ops.weight_delta against zeros (the one
+route to a packed target's float32 values), then ops.hadamard_rotate or a torch multiply, then a torch add -- in one
+process, the two alternating, medians of --repeats: [2048, 16384] int4 per channel with h = 2048 (down of BASELINE
+config 5) and [16384, 2048] int4 per channel with a multiplier. The rows go to `transforms`; no ratio is required.
 """
 import argparse
 import json
@@ -72,6 +78,52 @@ def bench_shape(torch, ops, lib, rows, d, warmup, repeats):
           "max_rel_difference": rel}
 
 
+TRANSFORM_SHAPES = ((2048, 16384, "hadamard", 2048), (16384, 2048, "multiply", 0))
+
+
+def bench_transform(torch, ops, rows, d, form, h, warmup, repeats):
+  g = torch.Generator(device="cuda").manual_seed(rows + d + h)
+  n = rows * d
+  w = torch.randn((n,), generator=g, device="cuda") * 0.02
+  packed = torch.randint(0, 256, (n // 2,), generator=g, device="cuda", dtype=torch.uint8)
+  scale = torch.rand((rows,), generator=g, device="cuda") * 0.005 + 0.001
+  target = ops.CompareTarget(packed, n, "i4", scale, None, rows, d, 32)
+  mult = (torch.rand((d,), generator=g, device="cuda") + 0.5) if form == "multiply" else None
+  zeros = torch.zeros((n,), dtype=torch.float32, device="cuda")
+
+  def fused():
+    return ops.weight_delta_transformed(w, target, d, multiplier=mult, hadamard_size=h)
+
+  def composed():
+    minus_dq = ops.weight_delta(zeros, target)                        # 0 - dequant(target)
+    if form == "hadamard":
+      return w + ops.hadamard_rotate(minus_dq, h)                      # (the rotation is linear: the sign is exact)
+    return w + (minus_dq.view(rows, d) * mult.view(1, d)).view(-1)
+  same = bool(torch.equal(fused().view(torch.int32), composed().view(torch.int32)))
+  for _ in range(warmup):
+    fused()
+    composed()
+  torch.cuda.synchronize()
+  times = {"fused": [], "composed": []}
+  for _ in range(repeats):                                            # alternating: both see the same clocks
+    for key, fn in (("fused", fused), ("composed", composed)):
+      start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+      start.record()
+      fn()
+      stop.record()
+      stop.synchronize()
+      times[key].append(start.elapsed_time(stop))
+  f_ms, c_ms = statistics.median(times["fused"]), statistics.median(times["composed"])
+  bytes_fused = n * (0.5 + 4 + 4)
+  bytes_composed = n * (0.5 + 4 + 4) + n * 8 + n * 12                  # delta against zeros, rotate / multiply, add
+  return {"rows": rows, "d": d, "target": "int4 per channel", "form": form, "hadamard_size": h,
+          "fused_ms": f_ms, "fused_ms_min_max": [min(times["fused"]), max(times["fused"])],
+          "composed_ms": c_ms, "composed_ms_min_max": [min(times["composed"]), max(times["composed"])],
+          "speedup": c_ms / f_ms, "fused_GBps": bytes_fused / (f_ms * 1e-3) / 1e9,
+          "composed_GBps": bytes_composed / (c_ms * 1e-3) / 1e9, "bytes_per_element": [8.5, bytes_composed / n],
+          "temporaries_of_the_composition_bytes": 2 * n * 4, "same_bits": same}
+
+
 def bench_model(torch, layers, sequences, tokens):
   import c5_model as C
   from mi355q import quantizer
@@ -100,6 +152,7 @@ def main():
   ap.add_argument("--model-layers", type=int, default=2)
   ap.add_argument("--sequences", type=int, default=64)
   ap.add_argument("--tokens", type=int, default=512)
+  ap.add_argument("--transforms", action="store_true", help="time the transformed weight delta against its composition")
   ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "layer_error_bench.json"))
   args = ap.parse_args()
   import __graft_entry__ as g
@@ -113,6 +166,9 @@ def main():
   result["not_slower"] = all(s["not_slower"] for s in result["shapes"])
   if args.model_layers > 0:
     result["model"] = bench_model(torch, args.model_layers, args.sequences, args.tokens)
+  if args.transforms:
+    result["transforms"] = [bench_transform(torch, ops, rows, d, form, h, args.warmup, args.repeats)
+                            for rows, d, form, h in TRANSFORM_SHAPES]
   line = json.dumps(result)
   if args.out:
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
