@@ -800,3 +800,347 @@ def compare_layer_outputs(reference_model, target_model, calibration_result: dic
     if follow_input_transforms:
       out.results[y_name].update(input_transform=transform[0], hadamard_size=transform[2])
   return out
+
+
+# ----------------------------------------------------------------------------- sensitivity sweep
+# Which layers can go to int4 or int2, and which must stay at int8? One walk over the float model gives the layer
+# output error of every FULLY_CONNECTED op under several candidate configurations at once: the float weight and the
+# Hessian product are on the device once per op, the candidates that are plain symmetric min/max fake-quantization
+# come out of ONE read of the weight (csrc/sensitivity.hip), and all candidates' deltas of an op go through one
+# stacked quadratic form, whose rows are independent.
+_MIN_MAX_KEY = "min_max_uniform_quantize"
+ROUTE_FUSED, ROUTE_GENERIC = "fused", "generic"
+SKIP_BASIS = "the candidate stores the weight in a transformed basis"
+_FUSED_BLOCKS = {"CHANNELWISE": 0, "BLOCKWISE_32": 32, "BLOCKWISE_64": 64, "BLOCKWISE_128": 128, "BLOCKWISE_256": 256}
+_GENERIC_ALGORITHMS = (_MIN_MAX_KEY, "OCTAV", "MSE", "GPTQ")       # weight-side, stored in the untransformed basis
+
+
+@dataclasses.dataclass(frozen=True)
+class SweepCandidate:
+  """One configuration of a sensitivity sweep: what a recipe entry's weight_tensor_config and algorithm_key say."""
+  name: str
+  num_bits: int
+  granularity: Any
+  algorithm_key: str = _MIN_MAX_KEY
+  symmetric: bool = True
+  algorithm_params: Optional[dict] = None
+
+  @property
+  def granularity_name(self) -> str:
+    return str(getattr(self.granularity, "value", self.granularity))
+
+  @property
+  def algorithm_name(self) -> str:
+    return str(getattr(self.algorithm_key, "value", self.algorithm_key))
+
+  @property
+  def block_size(self) -> int:
+    g = self.granularity_name
+    return int(g.split("_")[1]) if g.startswith("BLOCKWISE_") else 0
+
+  def fused_block(self, d: int) -> Optional[int]:
+    """The block argument of the fused kernel (0 = one scale per row), or None when the candidate is none of its."""
+    if (not self.symmetric or self.algorithm_name != _MIN_MAX_KEY or int(self.num_bits) not in (2, 4, 8)
+        or self.algorithm_params or self.granularity_name not in _FUSED_BLOCKS):
+      return None
+    block = _FUSED_BLOCKS[self.granularity_name]
+    return None if block and d % block else block
+
+  def bits_per_weight(self, rows: int, d: int) -> float:
+    """num_bits plus the scale's share: float32 per row or per tensor, float16 per block."""
+    g = self.granularity_name
+    if g == "CHANNELWISE":
+      return self.num_bits + 32.0 / d
+    if g == "TENSORWISE":
+      return self.num_bits + 32.0 / (rows * d)
+    return self.num_bits + 16.0 / self.block_size
+
+  def tensor_config(self):
+    from . import qtyping
+    return qtyping.TensorQuantizationConfig(
+        num_bits=int(self.num_bits), symmetric=bool(self.symmetric),
+        granularity=qtyping.QuantGranularity(self.granularity_name), algorithm_params=dict(self.algorithm_params or {}))
+
+
+class SweepKernels(LayerErrorKernels):
+  """The device side of sweep_layer_sensitivity, on top of compare_layer_outputs' kernels."""
+
+  def fused_ok(self, rows: int, d: int) -> bool:
+    """Whether symmetric min/max candidates of a [rows, d] weight take the one-read kernel."""
+    return True
+
+  def stack(self, count: int, rows: int, d: int):
+    import torch
+    from . import runtime as rt
+    return rt.empty((count, rows * d), torch.float32)
+
+  def sweep_into(self, stack, first: int, reference, rows: int, d: int, pairs):
+    """Deltas of the (bits, block) `pairs` into stack[first:first + len(pairs)]; returns their row sums of squares
+    (float64 [len(pairs), rows], still on the device)."""
+    from . import ops
+    _, sq = ops.requant_delta_sweep(reference.view(rows, d), pairs, want_sq=True,
+                                    out=stack[first:first + len(pairs)].view(len(pairs), rows, d))
+    return sq
+
+  def candidate_params(self, candidate: SweepCandidate, op_info, values: np.ndarray, tensor_qsv):
+    """UniformQuantParams of the registered algorithm for this op's weight (its own get_tensor_quant_params)."""
+    from .algorithms.uniform_quantize import gptq, mse, naive_min_max_quantize, octav
+    module = {_MIN_MAX_KEY: naive_min_max_quantize, "OCTAV": octav, "MSE": mse, "GPTQ": gptq}[candidate.algorithm_name]
+    return module.get_tensor_quant_params(op_info, candidate.tensor_config(), values, tensor_qsv)
+
+  def params_delta_into(self, stack, index: int, reference, rows: int, d: int, params):
+    """Delta of the integers and scales an algorithm returned into stack[index]; returns its row sums of squares
+    (float64 [1, rows], on the device). q - zero_point is formed in int32 and scaled in float64 (diff_bits 32)."""
+    import torch
+    from . import ops
+    from . import runtime as rt
+    q = params.quantized_data
+    q = q.device_tensor if isinstance(q, rt.HbmArray) else rt.to_device(np.ascontiguousarray(np.asarray(q)))
+    kind = {torch.int8: "i8", torch.int16: "i16", torch.int32: "i32"}.get(q.dtype)
+    if kind is None or q.numel() != rows * d:
+      raise ValueError(f"quantized data of type {q.dtype} and {q.numel()} elements for a [{rows}, {d}] weight")
+    channels, inner = scale_view(params, rows, d)
+    scale = rt.on_device(params.scale, torch.float32).reshape(-1)
+    zp = np.asarray(params.zero_point).reshape(-1).astype(np.int32)
+    zp_dev = rt.to_device(np.ascontiguousarray(np.broadcast_to(zp, (channels,)))) if zp.any() else None
+    target = ops.CompareTarget(q.reshape(-1), rows * d, kind, scale, zp_dev, channels, inner, 32)
+    delta = ops.weight_delta(reference, target)
+    stack[index].copy_(delta)
+    return delta.view(rows, d).double().square_().sum(dim=1, keepdim=True).t()
+
+  def energy(self, reference) -> float:
+    """Sum of the weight's squares in float64."""
+    return float(reference.double().square_().sum().item())
+
+  def host(self, values) -> np.ndarray:
+    return values if isinstance(values, np.ndarray) else values.cpu().numpy()
+
+
+def scale_view(params, rows: int, d: int) -> tuple[int, int]:
+  """(channels, inner) of ops.CompareTarget for the scale shape of a [rows, d] weight's UniformQuantParams."""
+  n = int(np.prod(np.shape(params.scale)))
+  if n == 1:
+    return 1, 1
+  if params.block_size:
+    if n * params.block_size != rows * d:
+      raise ValueError(f"{n} scales for blocks of {params.block_size} of a [{rows}, {d}] weight")
+    return n, int(params.block_size)
+  if params.quantized_dimension == 0 and n == rows:
+    return rows, d
+  if params.quantized_dimension == 1 and n == d:
+    return d, 1
+  raise ValueError(f"{n} scales along dimension {params.quantized_dimension} of a [{rows}, {d}] weight")
+
+
+class LayerSensitivity:
+  """results[output tensor name][candidate name] of sweep_layer_sensitivity: `weight`, `input`, `rows`, `d`, `route`
+  ("fused" or "generic"), `weight_sq_error`, `weight_snr`, `bits_per_weight`, and with Hessians `signal`, `error`,
+  `output_mse`, `output_snr`, `per_channel_error` as LayerOutputComparison defines them. skipped[(output tensor name,
+  candidate name)] is the reason a pair was not computed."""
+
+  def __init__(self, signature_key: Optional[str] = None, candidates: Sequence[SweepCandidate] = ()):
+    self.signature_key = signature_key
+    self.candidates = {c.name: c for c in candidates}
+    self.results: dict[str, dict[str, dict]] = {}
+    self.skipped: dict[tuple, str] = {}
+
+  def __getitem__(self, name: str) -> dict:
+    return self.results[name]
+
+  def __contains__(self, name: str) -> bool:
+    return name in self.results
+
+  def __iter__(self):
+    return iter(self.results)
+
+  def __len__(self) -> int:
+    return len(self.results)
+
+  def as_dict(self) -> dict:
+    layers = {y: {c: {k: v for k, v in r.items() if k != "per_channel_error"} for c, r in per.items()}
+              for y, per in self.results.items()}
+    skipped: dict[str, dict[str, str]] = {}
+    for (y, c), reason in self.skipped.items():
+      skipped.setdefault(y, {})[c] = reason
+    return {"signature_key": self.signature_key, "candidates": list(self.candidates), "layers": layers,
+            "skipped": skipped}
+
+  def save(self, save_folder: str, model_name: str) -> str:
+    """`<model_name>_layer_sensitivity.json`, without the per-channel arrays."""
+    save_path = pathlib.Path(save_folder)
+    os.makedirs(str(save_path), exist_ok=True)
+    path = str(save_path / (model_name + "_layer_sensitivity.json"))
+    with open(path, "w") as fh:
+      fh.write(json.dumps(self.as_dict()))
+    return path
+
+  def cheapest(self, min_output_snr: Optional[float] = None, min_weight_snr: Optional[float] = None) -> dict:
+    """{output tensor name: candidate name or None}: per op the candidate with the fewest bits per weight whose
+    `output_snr` (or `weight_snr`) is at least the threshold; among equally cheap ones the larger SNR."""
+    if (min_output_snr is None) == (min_weight_snr is None):
+      raise ValueError("cheapest needs exactly one of min_output_snr and min_weight_snr.")
+    key, least = ("output_snr", min_output_snr) if min_output_snr is not None else ("weight_snr", min_weight_snr)
+    out: dict[str, Optional[str]] = {}
+    for y, per in self.results.items():
+      best = None
+      for name, r in per.items():
+        if key not in r or not r[key] >= least:
+          continue
+        rank = (r["bits_per_weight"], -r[key])
+        if best is None or rank < best[0]:
+          best = (rank, name)
+      out[y] = None if best is None else best[1]
+    return out
+
+
+def fully_connected_scopes(float_model, signature_key: Optional[str] = DEFAULT_SIGNATURE_KEY) -> dict[str, str]:
+  """{output tensor name: scope string} of a signature's FULLY_CONNECTED ops: the string params_generator hands
+  recipe_manager for the op (tfl_flatbuffer_utils.get_op_scope)."""
+  m = _as_model(float_model)
+  sg_index, _ = _signature_subgraph(m, signature_key)
+  tensors = m.subgraphs[sg_index].tensors
+  return {y_name: tfl_flatbuffer_utils.get_op_scope(op, tensors) for op, _, _, y_name in _fully_connected_ops(m, sg_index)}
+
+
+def sweep_layer_sensitivity(float_model, candidates: Sequence[SweepCandidate], calibration_result: Optional[dict] = None,
+                            signature_key: Optional[str] = DEFAULT_SIGNATURE_KEY, *,
+                            kernels: Optional[SweepKernels] = None, max_stack_bytes: int = 2 << 30) -> LayerSensitivity:
+  """Layer output error of every FULLY_CONNECTED op of the float model with a constant 2-D float32 weight [rows, d]
+  under every candidate configuration (the same ops, skip reasons and figures as compare_layer_outputs; no recipe, no
+  quantize() and no quantized model are needed).
+
+  Candidates that are symmetric min/max with 2, 4 or 8 bits, CHANNELWISE or BLOCKWISE_32 / 64 / 128 / 256 (the block
+  dividing d) take the fused route: one ops.requant_delta_sweep call per op. The remaining weight-side algorithms that
+  keep the weight in its own basis (asymmetric or TENSORWISE min/max, OCTAV, MSE, GPTQ) take the generic route: the
+  registered algorithm's get_tensor_quant_params, then ops.weight_delta of its integers and scales. All deltas of an
+  op are stacked as [count * rows, d] and go through one ops.quadform_rows launch per chunk of at most
+  `max_stack_bytes`. Candidates stored in a transformed basis (Hadamard, OSCAR), or refused by the algorithm or the
+  policy for an op, are listed in `.skipped` with the reason.
+
+  Without `calibration_result` the sweep is data-free: weight-space figures only."""
+  from . import algorithm_manager
+  from . import qtyping
+  kernels = kernels or SweepKernels()
+  candidates = list(candidates)
+  names = [c.name for c in candidates]
+  if len(set(names)) != len(names):
+    raise ValueError("candidate names must be unique")
+  ref = _as_model(float_model)
+  sg_ref, _ = _signature_subgraph(ref, signature_key)
+  out = LayerSensitivity(signature_key, candidates)
+  with_data = calibration_result is not None
+  hessians: dict[str, tuple] = {}
+  signals: dict[tuple, np.ndarray] = {}
+  energies: dict[str, float] = {}
+  resident: tuple = (None, None)
+  operators = list(ref.subgraphs[sg_ref].operators or [])
+  fc_key = qtyping.TFLOperationName.FULLY_CONNECTED
+  for op, x_name, w, y_name in _fully_connected_ops(ref, sg_ref):
+    def skip_all(reason):
+      for c in candidates:
+        out.skipped[(y_name, c.name)] = reason
+    w_name = schema.tensor_name(w)
+    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 2):
+      skip_all(SKIP_WEIGHT)
+      continue
+    rows, d = int(w.shape[0]), int(w.shape[1])
+    qsv = calibration_result.get(x_name) if with_data else None
+    stat = (qsv or {}).get("hessian") if with_data else None
+    if with_data:
+      if stat is None:
+        skip_all(SKIP_NO_HESSIAN)
+        continue
+      if tuple(stat.shape) != (d, d):
+        skip_all(SKIP_ORDER)
+        continue
+    values = np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32).reshape(rows, d)
+    # ---- which route every candidate takes for this op
+    fused, generic = [], []
+    for c in candidates:
+      block = c.fused_block(d) if kernels.fused_ok(rows, d) else None
+      if block is not None:
+        fused.append((c, block))
+        continue
+      if c.algorithm_name not in _GENERIC_ALGORITHMS:
+        out.skipped[(y_name, c.name)] = SKIP_BASIS
+        continue
+      if c.block_size and d % c.block_size:
+        out.skipped[(y_name, c.name)] = (f"Quantized dimension {d} in tensor shape {(rows, d)} is not divisible by"
+                                         f" block size {c.block_size}.")
+        continue
+      if c.algorithm_name == "GPTQ" and stat is None:
+        out.skipped[(y_name, c.name)] = SKIP_NO_HESSIAN
+        continue
+      # the policy decides per mode (asymmetric weights pass as weight-only, not as dynamic): either one will do
+      cfg, refusal = None, None
+      for precision, explicit in ((qtyping.ComputePrecision.INTEGER, False), (qtyping.ComputePrecision.FLOAT, True)):
+        try:
+          trial = qtyping.OpQuantizationConfig(weight_tensor_config=c.tensor_config(), compute_precision=precision,
+                                               explicit_dequantize=explicit)
+          algorithm_manager.check_op_quantization_config(c.algorithm_name, fc_key, trial)
+        except ValueError as e:
+          refusal = refusal or str(e)
+          continue
+        cfg = trial
+        break
+      if cfg is None:
+        out.skipped[(y_name, c.name)] = refusal
+        continue
+      generic.append((c, cfg))
+    if not fused and not generic:
+      continue
+    if with_data and x_name not in hessians:
+      hessians[x_name] = kernels.hessian(stat)
+    if resident[0] != w_name:
+      resident = (w_name, kernels.weight(values.reshape(-1)))
+    w_dev = resident[1]
+    if with_data and (w_name, x_name) not in signals:
+      product, alpha = hessians[x_name]
+      signals[(w_name, x_name)] = kernels.quadform(w_dev, rows, d, product, 0.5 * alpha)
+    if w_name not in energies:
+      energies[w_name] = kernels.energy(w_dev)
+    # ---- chunks of at most max_stack_bytes: the fused candidates first (one sweep call per chunk), then the others
+    todo = [(c, ROUTE_FUSED, block) for c, block in fused] + [(c, ROUTE_GENERIC, cfg) for c, cfg in generic]
+    per_chunk = max(1, int(max_stack_bytes) // (rows * d * 4))
+    for first in range(0, len(todo), per_chunk):
+      chunk = todo[first:first + per_chunk]
+      stack = kernels.stack(len(chunk), rows, d)
+      n_fused = sum(1 for _, route, _ in chunk if route == ROUTE_FUSED)
+      done, sq_parts = [], []
+      if n_fused:
+        sq_parts.append(kernels.sweep_into(stack, 0, w_dev, rows, d, [(int(c.num_bits), block) for c, _, block in chunk[:n_fused]]))
+        done.extend((c, ROUTE_FUSED) for c, _, _ in chunk[:n_fused])
+      for c, _, cfg in chunk[n_fused:]:
+        try:
+          op_info = qtyping.OpInfo(op, fc_key, operators.index(op), cfg)
+          tensor_qsv = {"activation_tensor_qsv": qsv} if (c.algorithm_name == "GPTQ" and qsv is not None) else None
+          params = kernels.candidate_params(c, op_info, values, tensor_qsv)
+          if params.hadamard is not None or params.custom_algorithm_param:
+            out.skipped[(y_name, c.name)] = SKIP_BASIS
+            continue
+          sq_parts.append(kernels.params_delta_into(stack, len(done), w_dev, rows, d, params))
+        except (ValueError, KeyError, NotImplementedError) as e:       # what the algorithm refuses for this op
+          out.skipped[(y_name, c.name)] = str(e) or type(e).__name__
+          continue
+        done.append((c, ROUTE_GENERIC))
+      if not done:
+        continue
+      per_channel = None
+      if with_data:
+        product, alpha = hessians[x_name]
+        filled = stack[:len(done)]
+        per_channel = np.asarray(kernels.quadform(filled, len(done) * rows, d, product, 0.5 * alpha)).reshape(len(done), rows)
+      sq = np.concatenate([np.asarray(kernels.host(p), np.float64).reshape(-1, rows) for p in sq_parts], axis=0)
+      for i, (c, route) in enumerate(done):
+        weight_sq = float(np.sum(sq[i]))
+        entry = {"weight": w_name, "input": x_name, "rows": rows, "d": d, "route": route,
+                 "weight_sq_error": weight_sq,
+                 "weight_snr": energies[w_name] / (weight_sq + 1e-9 * rows * d),
+                 "bits_per_weight": c.bits_per_weight(rows, d)}
+        if with_data:
+          signal, error = float(np.sum(signals[(w_name, x_name)])), float(np.sum(per_channel[i]))
+          mse = error / rows
+          entry.update(signal=signal, error=error, output_mse=mse, output_snr=(signal / rows) / (mse + 1e-9),
+                       per_channel_error=per_channel[i].copy())
+        out.results.setdefault(y_name, {})[c.name] = entry
+  return out

@@ -1033,3 +1033,59 @@ def quadform_rows(a: torch.Tensor, product: torch.Tensor, alpha: float) -> torch
   _ffi.check(L.mi355q_quadform_rows_f32(rt.ptr(a), rows, d, rt.ptr(product), float(alpha), rt.ptr(out), rt.ptr(ws),
                                         nbytes, rt.stream_ptr()))
   return out
+
+
+SWEEP_BITS = (2, 4, 8)
+SWEEP_BLOCKS = (0, 32, 64, 128, 256)
+SWEEP_MAX_CANDIDATES = 8      # per launch (the candidate tables travel in the kernel arguments)
+
+
+def check_sweep_candidates(candidates, shape) -> list:
+  """[(bits, block)] as ints, or the ValueError `requant_sym` raises for them (no device is touched)."""
+  out = []
+  for bits, block in candidates:
+    bits, block = int(bits), int(block)
+    if bits not in SWEEP_BITS:
+      raise ValueError(f"bits must be 8, 4 or 2 (got {bits})")
+    if block not in SWEEP_BLOCKS:
+      raise ValueError(f"block must be 0, 32, 64, 128 or 256 (got {block})")
+    if block and shape[1] % block != 0:
+      raise ValueError(f"Quantized dimension {shape[1]} in tensor shape {tuple(shape)} is not"
+                       f" divisible by block size {block}.")
+    out.append((bits, block))
+  if not out:
+    raise ValueError("requant_delta_sweep needs at least one candidate")
+  return out
+
+
+def requant_delta_sweep(x: torch.Tensor, candidates, want_sq: bool = True, out: torch.Tensor | None = None):
+  """(delta float32 [count, rows, cols], sq float64 [count, rows] or None) for `candidates`, a sequence of
+  (bits, block): delta[k] = x - dequant(requant_sym(x, block_k, bits_k)) bit for bit (the int8 / diff_bits 8 rule of
+  `weight_delta`), from one read of x per launch of up to 8 candidates (mi355q_requant_delta_sweep_f32); sq[k][r] is
+  the float64 sum of delta[k][r]^2 in a fixed order. More than 8 candidates are split into several launches that
+  write into the one stacked output (`out`: a contiguous float32 [count, rows, cols] device tensor to write into
+  instead of a fresh one). Does not synchronize."""
+  import ctypes
+  if x.dim() != 2:
+    raise ValueError("requant_delta_sweep expects a 2-D [rows, cols] tensor")
+  cands = check_sweep_candidates(candidates, x.shape)
+  rt.require_gpu()
+  x = _f32(x)
+  rows, cols = x.shape
+  count = len(cands)
+  if out is None:
+    delta = rt.empty((count, rows, cols), torch.float32)
+  else:
+    if out.dtype != torch.float32 or not out.is_cuda or not out.is_contiguous() or tuple(out.shape) != (count, rows, cols):
+      raise ValueError(f"out must be a contiguous float32 device tensor of shape {(count, rows, cols)}")
+    delta = out
+  sq = rt.empty((count, rows), torch.float64) if want_sq else None
+  L = _ffi.lib()
+  for first in range(0, count, SWEEP_MAX_CANDIDATES):
+    part = cands[first:first + SWEEP_MAX_CANDIDATES]
+    bits = (ctypes.c_int32 * len(part))(*(b for b, _ in part))
+    block = (ctypes.c_int32 * len(part))(*(b for _, b in part))
+    _ffi.check(L.mi355q_requant_delta_sweep_f32(
+        rt.ptr(x), rows, cols, len(part), bits, block, delta.data_ptr() + first * rows * cols * 4, rows * cols,
+        (sq.data_ptr() + first * rows * 8) if want_sq else None, rt.stream_ptr()))
+  return delta, sq

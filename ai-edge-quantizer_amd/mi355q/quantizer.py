@@ -6,7 +6,9 @@ QUANTIZE_TENSOR transformation (pack + store + metadata) and serialize. Running 
 interpreter) is outside this build's scope: calibration results (QSVs) are passed in, and `validate()`
 compares the constant tensors on the GPU and takes inputs, outputs and intermediates from a
 caller-supplied `run_signature`; `validate_layer_outputs()` reports the output error of every FULLY_CONNECTED op
-over the calibration set from the Hessians calibration keeps, without a run of the model.
+over the calibration set from the Hessians calibration keeps, without a run of the model; `sweep_layer_sensitivity()`
+reports the same per op and candidate configuration from the float model alone, and `apply_layer_selection()` turns a
+choice of candidates into recipe entries.
 """
 from __future__ import annotations
 
@@ -15,6 +17,7 @@ import dataclasses
 import json
 import os
 import pathlib
+import re
 from typing import Any, Optional, Union
 
 from . import algorithm_manager
@@ -232,17 +235,7 @@ class Quantizer:
     if (calibration_result is None) == (calibration_data is None):
       raise ValueError("validate_layer_outputs needs exactly one of calibration_result and calibration_data.")
     if calibration_data is not None:
-      samples = calibration_data
-      if isinstance(calibration_data, dict):
-        if signature_key is not None:
-          if signature_key not in calibration_data:
-            raise ValueError(f"calibration_data has no samples for signature {signature_key!r}")
-          samples = calibration_data[signature_key]
-        elif len(calibration_data) == 1:
-          samples = next(iter(calibration_data.values()))
-        else:
-          raise ValueError("signature_key is required when calibration_data holds several signatures")
-      calibration_result = model_validator.layer_hessians(self.float_model, samples, signature_key)
+      calibration_result = self._layer_hessians(calibration_data, signature_key)
     results = model_validator.compare_layer_outputs(self.float_model, bytes(quantized_model), calibration_result,
                                                     signature_key, follow_input_transforms=follow_input_transforms)
     if save_folder:
@@ -250,3 +243,62 @@ class Quantizer:
         model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"
       results.save(save_folder, model_name=model_name)
     return results
+
+  def _layer_hessians(self, calibration_data: Any, signature_key: Optional[str]) -> dict:
+    """The Hessians of every FULLY_CONNECTED input from the samples calibrate() takes (a list, or {signature key: list})."""
+    samples = calibration_data
+    if isinstance(calibration_data, dict):
+      if signature_key is not None:
+        if signature_key not in calibration_data:
+          raise ValueError(f"calibration_data has no samples for signature {signature_key!r}")
+        samples = calibration_data[signature_key]
+      elif len(calibration_data) == 1:
+        samples = next(iter(calibration_data.values()))
+      else:
+        raise ValueError("signature_key is required when calibration_data holds several signatures")
+    return model_validator.layer_hessians(self.float_model, samples, signature_key)
+
+  def sweep_layer_sensitivity(self, candidates, calibration_result: Optional[dict] = None,
+                              calibration_data: Optional[Any] = None, signature_key: Optional[str] = None,
+                              save_folder: Optional[str] = None, model_name: Optional[str] = None
+                              ) -> model_validator.LayerSensitivity:
+    """Layer output error of every FULLY_CONNECTED op under every candidate configuration
+    (model_validator.SweepCandidate), from the float model alone: no recipe and no quantize() are needed
+    (model_validator.sweep_layer_sensitivity). At most one of `calibration_result` and `calibration_data` (as for
+    validate_layer_outputs); with neither the sweep is data-free and reports the weight-space figures only.
+    `result.cheapest(min_output_snr=...)` turns a threshold into a selection for apply_layer_selection()."""
+    if calibration_result is not None and calibration_data is not None:
+      raise ValueError("sweep_layer_sensitivity takes at most one of calibration_result and calibration_data.")
+    if calibration_data is not None:
+      calibration_result = self._layer_hessians(calibration_data, signature_key)
+    results = model_validator.sweep_layer_sensitivity(self.float_model, candidates, calibration_result, signature_key)
+    if save_folder:
+      if model_name is None:
+        model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"
+      results.save(save_folder, model_name=model_name)
+    return results
+
+  def apply_layer_selection(self, sensitivity: model_validator.LayerSensitivity, selection: dict,
+                            mode: str = "weight_only") -> None:
+    """One recipe entry per op of `selection` ({output tensor name: candidate name or None}, e.g. what
+    `sensitivity.cheapest()` returned) with the candidate's algorithm key, bits and granularity, added through
+    add_weight_only_config (`mode` "weight_only") or add_dynamic_config ("dynamic"). The entry's regex is the op's
+    whole scope string, escaped and anchored, so it matches that op and no other; ops mapped to None are left to
+    the entries already in the recipe."""
+    if mode not in ("weight_only", "dynamic"):
+      raise ValueError(f"mode must be 'weight_only' or 'dynamic', got {mode!r}")
+    add = self.add_weight_only_config if mode == "weight_only" else self.add_dynamic_config
+    scopes = model_validator.fully_connected_scopes(self.float_model, sensitivity.signature_key)
+    for y_name, chosen in selection.items():
+      if chosen is None:
+        continue
+      if y_name not in scopes:
+        raise ValueError(f"no FULLY_CONNECTED op writes {y_name!r}")
+      if chosen not in sensitivity.candidates:
+        raise ValueError(f"unknown candidate {chosen!r}")
+      c = sensitivity.candidates[chosen]
+      if not c.symmetric or c.algorithm_params:
+        raise ValueError(f"candidate {chosen!r} is asymmetric or carries algorithm parameters, which"
+                         " add_weight_only_config / add_dynamic_config cannot express")
+      add("^" + re.escape(scopes[y_name]) + "$", qtyping.TFLOperationName.FULLY_CONNECTED, int(c.num_bits),
+          qtyping.QuantGranularity(c.granularity_name), c.algorithm_name)

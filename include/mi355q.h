@@ -858,6 +858,54 @@ size_t mi355q_quadform_rows_workspace_bytes(int64_t rows, int64_t d);
 int32_t mi355q_quadform_rows_f32(const float* a, int64_t rows, int64_t d, const float* product, double alpha,
                                  double* out_rows, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Sensitivity sweep (csrc/sensitivity.hip): the weight deltas of up to 8 candidate
+ * configurations from ONE read of the weight.
+ *
+ * Candidate k is the symmetric min/max fake-quantization of x [rows, cols]
+ * (float32, row-major) with bits[k] in {2, 4, 8} and block[k] in {0, 32, 64, 128,
+ * 256}: block 0 is one scale per row, block > 0 one scale per block along cols,
+ * rounded f32 -> bf16 -> f16 -> f32 as the blockwise scales of
+ * mi355q_requant_sym_f32 are. `bits` and `block` are HOST arrays of `count`
+ * entries (1 <= count <= 8); they travel in the kernel arguments, as the pointer
+ * tables of mi355q_requant_sym_f32_batched_hostptrs do.
+ *   delta_out[k * delta_stride + e] = x[e] - fl(float(q_k[e]) * s_k)
+ * where q_k and s_k are bit for bit what mi355q_requant_sym_f32(x, rows, cols,
+ * block[k], bits[k], clip = NULL, ...) writes to q_out / scale_out: the result
+ * equals that call followed by mi355q_weight_delta_f32 (MI355Q_CMP_I8, diff_bits
+ * 8) bit for bit. The product is rounded to float32 once and subtracted in
+ * float32 (no FMA). There is no nan_to_num: NaN / inf data and NaN scales pass
+ * through as in that composition. No integers and no scales are stored.
+ * delta_stride (in floats) >= rows * cols.
+ *
+ * sq_rows_out: NULL, or double[count][rows] with sq[k][r] = Sum_c double(delta)^2
+ * of row r in FLOAT64, added in a fixed order (a lane's pieces in ascending
+ * order, a wave butterfly, the waves' partials in index order; no floating-point
+ * atomics): the same bits in every run.
+ *
+ * Vector route (cols % 4 == 0, cols <= 16384, x and delta_out 16-byte aligned,
+ * delta_stride % 4 == 0 when count > 1): a row is held in registers as 16-byte
+ * pieces by one wave (cols <= 1024) or one 256-thread workgroup, x is read from
+ * HBM once for all candidates, the |x|-max butterfly runs once (the maxima of 8 /
+ * 16 / 32 / 64 adjacent lanes are the block-32 / 64 / 128 / 256 maxima, the wave's
+ * or workgroup's the row's), and every delta piece leaves as one non-temporal
+ * 16-byte store: 4 + 4 count bytes per element against 14 count for requant_sym
+ * -> weight_delta. Every other shape (cols % 4 != 0, misaligned pointers,
+ * cols > 16384) takes a scalar kernel with the same bits, which passes over x once
+ * for the row maximum and once per candidate: the one-read property holds for the
+ * vector route only.
+ *
+ * Refused before any launch with MI355Q_BAD_ARG: count outside [1, 8], null
+ * tables, bits or block outside the sets above, a block that does not divide
+ * cols ("Quantized dimension <cols> is not divisible by block size <block>."),
+ * negative shapes; then rows == 0 or cols == 0 enqueues nothing; then null x /
+ * delta_out or delta_stride < rows * cols are MI355Q_BAD_ARG, rows > 2^31 - 1
+ * MI355Q_UNSUPPORTED. delta_out must not alias x.
+ * ------------------------------------------------------------------------ */
+int32_t mi355q_requant_delta_sweep_f32(const float* x, int64_t rows, int64_t cols, int32_t count,
+                                       const int32_t* bits, const int32_t* block, float* delta_out,
+                                       int64_t delta_stride, double* sq_rows_out, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
