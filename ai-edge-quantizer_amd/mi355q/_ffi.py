@@ -132,6 +132,12 @@ PROTOTYPES = {
     "mi355q_quadform_rows_workspace_bytes": (c_size, [c_i64, c_i64]),
     "mi355q_quadform_rows_f32": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_f64, c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_requant_delta_sweep_f32": (c_i32, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+    "mi355q_qfc_quantize_rows_f32": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
+    "mi355q_qfc_forward_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
+    "mi355q_qfc_forward_i8": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_i64, c_i32,
+                                      c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "mi355q_sqdiff_cols_workspace_bytes": (c_size, [c_i64, c_i64]),
+    "mi355q_sqdiff_cols_f64": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_size, c_ptr]),
     "mi355q_clock_probe": (c_i32, [c_f64, c_ptr, c_ptr]),
     "mi355q_device_alloc": (c_i32, [c_size, ctypes.POINTER(ctypes.c_void_p)]),
     "mi355q_device_free": (c_i32, [c_ptr]),

@@ -802,6 +802,266 @@ def compare_layer_outputs(reference_model, target_model, calibration_result: dic
   return out
 
 
+# ----------------------------------------------------------------------------- integer execution
+# compare_layer_outputs evaluates 1/2 tr(dW H dW^T): the weight's error alone. What a dynamic-range op adds by rounding
+# every activation row to int8 at run time, what a static op adds by reading an int8 activation, and what a Hadamard
+# rotation does to either cannot be written with the Hessian, because rounding X is no linear map of X. Here the
+# quantized op is executed in integers on the calibration samples (csrc/qfc.hip) and compared with the float product.
+_DEQUANTIZE, _QUANTIZE = 6, 114
+MODE_STATIC, MODE_DYNAMIC, MODE_WEIGHT_ONLY = "static", "dynamic", "weight_only"
+SKIP_INT16 = "the op reads an INT16 activation"
+SKIP_WEIGHT_ZERO_POINT = "the weight has a non-zero zero point"
+SKIP_FLOAT_TARGET = "the target weight is float"
+SKIP_NO_SAMPLE = "no sample for the input"
+SKIP_SAMPLE_SHAPE = "the sample's size is no multiple of the weight's reduction dimension"
+SKIP_KIND = "the target weight is neither int8, int4 nor int2"
+EXECUTION_CHUNK_ROWS = 4096
+
+
+class LayerExecutionKernels:
+  """The device side of compare_layer_execution: where the operands live and the kernels."""
+
+  def sample(self, value, d: int):
+    """A sample entry (array or device tensor of any rank) as float32 [n, d] rows."""
+    import torch
+    from . import runtime as rt
+    x = rt.on_device(rt.resident_sample(value), torch.float32)
+    return x.contiguous().view(-1, d)
+
+  def weight(self, values: np.ndarray, rows: int, d: int):
+    from . import runtime as rt
+    return rt.to_device(values).view(rows, d)
+
+  def target(self, plan: ConstantPlan):
+    return _device_target(plan)
+
+  def dequantized(self, target, rows: int, d: int):
+    """float32 [rows, d]: the stored weight dequantized by the validators' rule (weight-only mode)."""
+    import torch
+    from . import ops
+    from . import runtime as rt
+    zeros = torch.zeros((rows * d,), dtype=torch.float32, device=rt.device())
+    return torch.neg(ops.weight_delta(zeros, target)).view(rows, d)       # 0 - dq is exact
+
+  def rows(self, x, first: int, count: int):
+    return x[first:first + count]
+
+  def transform(self, x, kind: str, multiplier, hadamard_size: int):
+    """The inserted op's own map on rows of length d: x * multiplier, or x R with R = blockdiag(H_h / sqrt(h))."""
+    from . import ops
+    from . import runtime as rt
+    if kind == TRANSFORM_MULTIPLY:
+      return x * rt.to_device(np.asarray(multiplier, np.float32))
+    if kind == TRANSFORM_HADAMARD:
+      return ops.hadamard_rotate(x.contiguous(), hadamard_size)
+    return x
+
+  def gemm(self, x, w):
+    """float32 [n, rows] = x w^T."""
+    from . import ops
+    return ops.gemm(x, w, trans_b=True)
+
+  def quantize_dynamic(self, x):
+    from . import ops
+    return ops.qfc_quantize_rows(x)
+
+  def quantize_static(self, x, scale: float, zero_point: int):
+    import torch
+    from . import ops
+    from . import runtime as rt
+    s = torch.tensor([scale], dtype=torch.float32, device=rt.device())
+    zp = torch.tensor([zero_point], dtype=torch.int32, device=rt.device())
+    return ops.quantize(x.contiguous(), 1, 1, x.numel(), s, zp, 8, False), s
+
+  def forward(self, xq, x_scale, x_zero_point: int, target, rows: int, d: int):
+    from . import ops
+    return ops.qfc_forward(xq, x_scale, x_zero_point, target, rows, d)
+
+  def sqdiff(self, yq, y, sums):
+    """(Sum_t (yq - y)^2, Sum_t y^2) per column, added onto `sums` (None: the first chunk)."""
+    from . import ops
+    return ops.sqdiff_cols(yq, y, out=sums)
+
+  def host(self, sums) -> tuple:
+    return sums[0].cpu().numpy(), sums[1].cpu().numpy()
+
+
+class LayerExecutionComparison(LayerOutputComparison):
+  """Per FULLY_CONNECTED op (keyed by its output tensor's name): how far the quantized op's integer execution is
+  from the float product over the calibration samples. `results[name]` holds `weight`, `input`, `rows`, `d`,
+  `tokens`, `mode` ("static", "dynamic" or "weight_only"), `signal`, `error`, `output_mse`, `output_snr` and
+  `per_channel_error` (float64 [rows]), with `follow_input_transforms` also `input_transform` and `hadamard_size`;
+  `skipped[name]` is the reason an op was not computed."""
+
+  def save(self, save_folder: str, model_name: str) -> str:
+    """`<model_name>_layer_execution_errors.json`, without the per-channel arrays."""
+    save_path = pathlib.Path(save_folder)
+    os.makedirs(str(save_path), exist_ok=True)
+    path = str(save_path / (model_name + "_layer_execution_errors.json"))
+    with open(path, "w") as fh:
+      fh.write(json.dumps(self.as_dict()))
+    return path
+
+
+def compare_layer_execution(reference_model, target_model, samples: Iterable[dict],
+                            signature_key: Optional[str] = DEFAULT_SIGNATURE_KEY, *,
+                            kernels: Optional[LayerExecutionKernels] = None,
+                            follow_input_transforms: bool = False) -> LayerExecutionComparison:
+  """Executes every quantized FULLY_CONNECTED op in integers on the calibration samples and compares it with the
+  float model's product, for every op of the float model with a constant 2-D float32 weight [rows, d] whose input 0
+  is in `samples` (the {tensor name: array or device tensor} maps calibrate() takes; tensors of any rank are rows of
+  length d). The target op is the producer of the same-named output in the quantized model, and its mode is read
+  from the graph:
+    "static"       input 0 is INT8 with quantization parameters: q = clip(rint(x / s_x + zp_x), -128, 127) with the
+                   tensor's own (s_x, zp_x), ops.quantize as it stands;
+    "dynamic"      input 0 is FLOAT32 and the op reads the integer weight itself: every row is quantized to int8 at
+                   run time with s_x = max|row| / 127 (ops.qfc_quantize_rows);
+    "weight_only"  the op reads a DEQUANTIZE of the integer weight: no activation rounding, Yq = X dequant(W^)^T in
+                   float32, the direct measurement of what compare_layer_outputs derives from the Hessian.
+  In the integer modes acc = Sum_k (q_x - zp_x) q_w is exact in int32 and Yq = float(acc) * (s_x * s_w), with one
+  accumulator per block under blockwise scales (ops.qfc_forward). With Y = X W^T (ops.gemm) over n tokens in all:
+    signal = (1/n) ||Y||^2     error = (1/n) ||Yq - Y||^2     per_channel_error[r] = (1/n) Sum_t (Yq - Y)[t, r]^2
+    output_mse = error / rows     output_snr = (signal / rows) / (output_mse + 1e-9)
+  the conventions of compare_layer_outputs. The sums are float64 and added in a fixed order, sample by sample and in
+  chunks of at most 4096 rows: no [all tokens, rows] array exists.
+
+  This is the pre-bias product: bias, fused activation and the requantization of the op's output do not enter, the
+  boundary compare_layer_outputs draws. Skipped with a reason: an INT16 activation, a weight with a non-zero zero
+  point, a float target weight, a missing sample, and an op behind an inserted Hadamard rotation or OSCAR multiply
+  unless `follow_input_transforms` is set. Then X goes through the inserted op's own constant first
+  (ops.hadamard_rotate, or the multiply; _input_transform) and the comparison is still against the float model's
+  product of the untransformed input; every entry then also carries `input_transform` and `hadamard_size`.
+  """
+  kernels = kernels or LayerExecutionKernels()
+  samples = list(samples)
+  ref, tgt = _as_model(reference_model), _as_model(target_model)
+  sg_ref, _ = _signature_subgraph(ref, signature_key)
+  sg_tgt, _ = _signature_subgraph(tgt, signature_key)
+  tgt_sg = tgt.subgraphs[sg_tgt]
+  producers = _producers(tgt_sg)
+  producer_op: dict[str, Any] = {}
+  for op in tgt_sg.operators or []:
+    for o in op.outputs:
+      producer_op.setdefault(schema.tensor_name(tgt_sg.tensors[o]), op)
+
+  def code(op) -> int:
+    return int(tgt.operatorCodes[op.opcodeIndex].builtinCode)
+
+  def name(index) -> Optional[str]:
+    return schema.tensor_name(tgt_sg.tensors[index]) if index is not None and index >= 0 else None
+
+  out = LayerExecutionComparison(signature_key)
+  for _, x_name, w, y_name in _fully_connected_ops(ref, sg_ref):
+    w_name = schema.tensor_name(w)
+    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 2):
+      out.skipped[y_name] = SKIP_WEIGHT
+      continue
+    rows, d = int(w.shape[0]), int(w.shape[1])
+    fc = producer_op.get(y_name)
+    if fc is None or code(fc) != _FULLY_CONNECTED or len(fc.inputs) < 2 or fc.inputs[0] < 0 or fc.inputs[1] < 0:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    # ---- the weight the target op reads: the integer constant itself, or a DEQUANTIZE of it
+    read = tgt_sg.tensors[fc.inputs[1]]
+    target, through_dequantize = read, False
+    if not _has_data(tgt.buffers, read):
+      deq = producers.get(int(fc.inputs[1]))
+      if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
+        out.skipped[y_name] = SKIP_TARGET
+        continue
+      target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
+    if schema.tensor_name(target) != w_name or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if target.type in (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16):
+      out.skipped[y_name] = SKIP_FLOAT_TARGET
+      continue
+    # ---- the activation it reads
+    x_in = tgt_sg.tensors[fc.inputs[0]]
+    if x_in.type == schema.TensorType.INT16:
+      out.skipped[y_name] = SKIP_INT16
+      continue
+    transform = (TRANSFORM_NONE, None, 0)
+    x_quant = None
+    if x_in.type == schema.TensorType.INT8:
+      q = x_in.quantization
+      source = name(fc.inputs[0])
+      quantize = producers.get(int(fc.inputs[0]))
+      if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
+        source = name(quantize.inputs[0])
+      if q is None or q.scale is None or len(q.scale) != 1 or source != x_name or through_dequantize:
+        out.skipped[y_name] = SKIP_INPUT
+        continue
+      zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
+      x_quant = (float(np.float32(q.scale[0])), zero_point)
+      mode = MODE_STATIC
+    elif x_in.type == schema.TensorType.FLOAT32:
+      mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
+      if name(fc.inputs[0]) != x_name:
+        found = _input_transform(tgt, tgt_sg, producers, fc, x_name, d) if follow_input_transforms else None
+        if found is None:
+          out.skipped[y_name] = SKIP_INPUT
+          continue
+        transform = found
+    else:
+      out.skipped[y_name] = SKIP_INPUT
+      continue
+    values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
+    plan = _target_plan(w_name, values, tgt, target)
+    if plan is None or not plan.dequantized:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if plan.kind not in ("i8", "i4", "i2"):
+      out.skipped[y_name] = SKIP_KIND
+      continue
+    if plan.scale is None:
+      _read_blockwise_scales(plan, tgt, tgt_sg.tensors, target)
+    if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
+      out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
+      continue
+    present = [s[x_name] for s in samples if x_name in s]
+    if not present:
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    if any(int(np.prod(v.shape)) % d for v in present):
+      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
+      continue
+    w_dev = kernels.weight(values, rows, d)
+    t_dev = kernels.target(plan)
+    dq_dev = kernels.dequantized(t_dev, rows, d) if mode == MODE_WEIGHT_ONLY else None
+    sums, tokens = None, 0
+    for value in present:
+      x = kernels.sample(value, d)
+      n = int(x.shape[0])
+      for first in range(0, n, EXECUTION_CHUNK_ROWS):
+        xc = kernels.rows(x, first, min(EXECUTION_CHUNK_ROWS, n - first))
+        y = kernels.gemm(xc, w_dev)
+        xt = xc if transform[0] == TRANSFORM_NONE else kernels.transform(xc, *transform)
+        if mode == MODE_WEIGHT_ONLY:
+          yq = kernels.gemm(xt, dq_dev)
+        elif mode == MODE_DYNAMIC:
+          xq, x_scale = kernels.quantize_dynamic(xt)
+          yq = kernels.forward(xq, x_scale, 0, t_dev, rows, d)
+        else:
+          xq, x_scale = kernels.quantize_static(xt, *x_quant)
+          yq = kernels.forward(xq, x_scale, x_quant[1], t_dev, rows, d)
+        sums = kernels.sqdiff(yq, y, sums)
+      tokens += n
+    if sums is None:          # (every sample of the input was empty)
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    sq_diff, sq_ref = kernels.host(sums)
+    per_channel = np.asarray(sq_diff, np.float64) / tokens
+    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
+    mse = error / rows
+    out.results[y_name] = {"weight": w_name, "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
+                           "signal": signal, "error": error, "output_mse": mse,
+                           "output_snr": (signal / rows) / (mse + 1e-9), "per_channel_error": per_channel}
+    if follow_input_transforms:
+      out.results[y_name].update(input_transform=transform[0], hadamard_size=transform[2])
+  return out
+
+
 # ----------------------------------------------------------------------------- sensitivity sweep
 # Which layers can go to int4 or int2, and which must stay at int8? One walk over the float model gives the layer
 # output error of every FULLY_CONNECTED op under several candidate configurations at once: the float weight and the

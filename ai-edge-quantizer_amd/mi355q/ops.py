@@ -1035,6 +1035,98 @@ def quadform_rows(a: torch.Tensor, product: torch.Tensor, alpha: float) -> torch
   return out
 
 
+# ------------------------------------------------------- integer execution of FULLY_CONNECTED ---
+# (include/mi355q.h, "Integer execution of a quantized FULLY_CONNECTED op")
+QFC_BLOCKS = (32, 64, 128, 256)
+QFC_MAX_D = 65536
+
+
+def qfc_quantize_rows(x2d: torch.Tensor):
+  """Dynamic-range activation rows: (q int8 [n, d], scale float32 [n]) of a float32 [n, d] device tensor, with
+  scale = max|row| / 127 and q = clamp(round_half_away_from_zero(x * (127 / max|row|)), -127, 127); an all-zero row
+  has scale 1, a row with a NaN or an infinity scale NaN and q = 0. Does not synchronize."""
+  rt.require_gpu()
+  x2d = _f32(x2d)
+  if x2d.dim() != 2:
+    raise ValueError(f"expected a [n, d] tensor, got {tuple(x2d.shape)}")
+  n, d = x2d.shape
+  q, scale = rt.empty((n, d), torch.int8), rt.empty((n,), torch.float32)
+  _ffi.check(_ffi.lib().mi355q_qfc_quantize_rows_f32(rt.ptr(x2d), n, d, rt.ptr(q), rt.ptr(scale), rt.stream_ptr()))
+  return q, scale
+
+
+def qfc_forward(xq: torch.Tensor, x_scale: torch.Tensor, x_zero_point: int, target: CompareTarget, rows: int, d: int,
+                want_acc: bool = False):
+  """The integer FULLY_CONNECTED product of int8 activations xq [n, d] and the stored integer weight [rows, d] of
+  `target` (kind i8 / i4 / i2, as the validators build it), rescaled to float32 [n, rows]:
+  y = float(Sum_k (xq - x_zero_point) q_w) * (x_scale * w_scale), with one int32 accumulator per block under
+  blockwise scales (added in float32 in ascending order). The pre-bias product: bias, fused activation and the
+  requantization of the output do not enter. `x_scale` holds 1 or n float32 entries. The scale view of `target`
+  decides the granularity: channels = 1 per tensor; channels = rows with inner = d per channel; inner = a block size
+  blockwise. Returns y, or (y, acc int32 [n, rows]) with `want_acc` (not with blockwise scales). Does not
+  synchronize."""
+  rt.require_gpu()
+  if target.kind not in ("i8", "i4", "i2"):
+    raise ValueError(f"qfc_forward needs an i8 / i4 / i2 weight, got {target.kind!r}")
+  rows, d = int(rows), int(d)
+  if xq.dtype != torch.int8 or not xq.is_cuda or xq.dim() != 2 or xq.shape[1] != d:
+    raise TypeError(f"expected an int8 [n, {d}] device tensor, got {xq.dtype} {tuple(xq.shape)} on {xq.device}")
+  if target.n != rows * d:
+    raise ValueError(f"the weight has {target.n} elements, expected {rows} x {d}")
+  if target.zero_point is not None and bool(torch.any(target.zero_point != 0)):
+    raise ValueError("the weight's zero point must be 0")
+  if target.channels == 1:
+    block = 0
+  elif target.channels == rows and target.inner == d:
+    block = 0
+  elif target.inner in QFC_BLOCKS and target.channels * target.inner == rows * d:
+    block = target.inner
+  else:
+    raise ValueError(f"scale view ({target.channels} channels, inner {target.inner}) is neither per tensor, per channel"
+                     f" nor blockwise over a [{rows}, {d}] weight")
+  if target.scale.numel() != target.channels:
+    raise ValueError("scale must have one entry per channel")
+  # (no .contiguous(): a misaligned view is still dense, and the library routes on the address)
+  n = xq.shape[0]
+  x_scale = _f32(x_scale).view(-1)
+  y = rt.empty((n, rows), torch.float32)
+  acc = rt.empty((n, rows), torch.int32) if want_acc else None
+  L = _ffi.lib()
+  nbytes = L.mi355q_qfc_forward_workspace_bytes(rows, d, block)
+  ws = rt.empty((max(nbytes, 1),), torch.uint8)
+  if not xq.is_contiguous():
+    xq = xq.contiguous()
+  _ffi.check(L.mi355q_qfc_forward_i8(rt.ptr(xq), n, d, rt.ptr(x_scale), x_scale.numel(), int(x_zero_point),
+                                     rt.ptr(target.data), COMPARE_KINDS[target.kind], rows, rt.ptr(target.scale),
+                                     target.scale.numel(), block, rt.ptr(y), rt.ptr(acc), rt.ptr(ws), nbytes,
+                                     rt.stream_ptr()))
+  return (y, acc) if want_acc else y
+
+
+def sqdiff_cols(a: torch.Tensor, b: torch.Tensor, out: tuple | None = None):
+  """(Sum_t (a - b)^2, Sum_t b^2) per column of float32 [n, cols] device tensors, float64 [cols] each, added in a
+  fixed order (the same bits in every run). With `out` = an earlier result the sums are added onto it in place and
+  it is returned: the samples of a calibration set, in order. Does not synchronize."""
+  rt.require_gpu()
+  a, b = _f32(a), _f32(b)
+  if a.dim() != 2 or a.shape != b.shape:
+    raise ValueError(f"expected two [n, cols] tensors, got {tuple(a.shape)} and {tuple(b.shape)}")
+  n, cols = a.shape
+  if out is None:
+    sq_d, sq_b = rt.empty((cols,), torch.float64), rt.empty((cols,), torch.float64)
+  else:
+    sq_d, sq_b = out
+    for v in (sq_d, sq_b):
+      if v.dtype != torch.float64 or not v.is_cuda or v.numel() != cols or not v.is_contiguous():
+        raise TypeError(f"`out` must hold two contiguous float64 device tensors of {cols} elements")
+  L = _ffi.lib()
+  nbytes = L.mi355q_sqdiff_cols_workspace_bytes(n, cols)
+  ws = rt.empty((max(nbytes, 1),), torch.uint8)
+  _ffi.check(L.mi355q_sqdiff_cols_f64(rt.ptr(a), rt.ptr(b), n, cols, rt.ptr(sq_d), rt.ptr(sq_b), 0 if out is None else 1,
+                                      rt.ptr(ws), nbytes, rt.stream_ptr()))
+  return sq_d, sq_b
+
+
 SWEEP_BITS = (2, 4, 8)
 SWEEP_BLOCKS = (0, 32, 64, 128, 256)
 SWEEP_MAX_CANDIDATES = 8      # per launch (the candidate tables travel in the kernel arguments)

@@ -244,8 +244,34 @@ class Quantizer:
       results.save(save_folder, model_name=model_name)
     return results
 
-  def _layer_hessians(self, calibration_data: Any, signature_key: Optional[str]) -> dict:
-    """The Hessians of every FULLY_CONNECTED input from the samples calibrate() takes (a list, or {signature key: list})."""
+  def validate_layer_execution(self, calibration_data: Any, signature_key: Optional[str] = None,
+                               save_folder: Optional[str] = None, model_name: Optional[str] = None,
+                               follow_input_transforms: bool = False) -> model_validator.LayerExecutionComparison:
+    """Executes every quantized FULLY_CONNECTED op of the last quantize() result in integers on the calibration
+    samples and compares it with the float product: error = (1/n) ||Yq - Y||^2 per op with its signal, MSE, SNR,
+    per-channel errors, token count and mode (model_validator.compare_layer_execution). Unlike
+    validate_layer_outputs this includes the activations' own rounding: the per-row int8 quantization of
+    dynamic-range ops and the calibrated int8 activations of static ops. The figure is the pre-bias product: bias,
+    fused activation and the requantization of the op's output do not enter.
+
+    `calibration_data`: the samples calibrate() takes, a list of {tensor name: array or device tensor}, or
+    {signature key: such a list}. Ops behind an inserted Hadamard rotation or OSCAR multiply are listed in `.skipped`
+    unless `follow_input_transforms` is set; then the samples go through the inserted op's own constant first."""
+    quantized_model = self._result.quantized_model
+    if quantized_model is None:
+      raise ValueError("No quantized model available to validate.")
+    samples = self._signature_samples(calibration_data, signature_key)
+    results = model_validator.compare_layer_execution(self.float_model, bytes(quantized_model), samples, signature_key,
+                                                      follow_input_transforms=follow_input_transforms)
+    if save_folder:
+      if model_name is None:
+        model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"
+      results.save(save_folder, model_name=model_name)
+    return results
+
+  @staticmethod
+  def _signature_samples(calibration_data: Any, signature_key: Optional[str]):
+    """The sample list of one signature from the forms calibrate() takes (a list, or {signature key: list})."""
     samples = calibration_data
     if isinstance(calibration_data, dict):
       if signature_key is not None:
@@ -256,6 +282,11 @@ class Quantizer:
         samples = next(iter(calibration_data.values()))
       else:
         raise ValueError("signature_key is required when calibration_data holds several signatures")
+    return samples
+
+  def _layer_hessians(self, calibration_data: Any, signature_key: Optional[str]) -> dict:
+    """The Hessians of every FULLY_CONNECTED input from the samples calibrate() takes (a list, or {signature key: list})."""
+    samples = self._signature_samples(calibration_data, signature_key)
     return model_validator.layer_hessians(self.float_model, samples, signature_key)
 
   def sweep_layer_sensitivity(self, candidates, calibration_result: Optional[dict] = None,

@@ -906,6 +906,96 @@ int32_t mi355q_requant_delta_sweep_f32(const float* x, int64_t rows, int64_t col
                                        const int32_t* bits, const int32_t* block, float* delta_out,
                                        int64_t delta_stride, double* sq_rows_out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Integer execution of a quantized FULLY_CONNECTED op (csrc/qfc.hip): what the
+ * op computes in integers on the calibration samples, up to the int32
+ * accumulator and its float rescale. Bias, fused activation and the
+ * requantization of the op's output are outside: the result is the pre-bias
+ * product, the boundary the layer output error draws.
+ *
+ * mi355q_qfc_quantize_rows_f32: the dynamic-range activation quantizer. x is
+ * float32 [n, d] row-major. Per row t: range = max_k |x[t,k]|;
+ *   range == 0            scale_out[t] = 1.0f, q = 0
+ *   a NaN or an infinity  scale_out[t] = NaN,  q = 0
+ *   otherwise             scale_out[t] = range / 127.0f, inv = 127.0f / range
+ *                         (IEEE float32 divides),
+ *                         q = clamp(round_half_away_from_zero(fl(x * inv)), -127, 127)
+ * The product is rounded to float32 once and the rounding of it is exact
+ * (trunc + the exact remainder, never "add 0.5"): 0.49999997f gives 0. Vector
+ * route (d % 16 == 0, d <= 16384, x and q_out 16-byte aligned): one workgroup
+ * per row keeps the row in registers between the maximum and the rounding, so x
+ * is read once, with 16-byte loads and one 16-byte store per 16 elements. Every
+ * other shape or alignment takes a scalar kernel with the same bits that reads
+ * the row twice. n == 0 or d == 0 enqueues nothing; n > 2^31 - 1 is
+ * MI355Q_UNSUPPORTED.
+ *
+ * mi355q_qfc_forward_i8: xq is int8 [n, d]; w the stored integer weight
+ * [rows, d] of w_kind MI355Q_CMP_I8, _I4 or _I2 (I4 / I2 packed over the flat
+ * tensor, element 0 in the low bits, as mi355q_pack_bits writes them); weight
+ * zero points are 0.
+ *   acc[t,r] = Sum_k (xq[t,k] - x_zero_point) * w[r,k]        (int32, exact)
+ * formed as Sum xq * w - x_zero_point * Sum_k w[r,k], the second sum from a
+ * kernel of its own into `workspace` (not launched when x_zero_point == 0).
+ * x_scale has x_scale_count in {1, n} entries (one per token for dynamic rows).
+ * block == 0 with w_scale_count in {1, rows}: one scale per tensor or per output
+ * channel,
+ *   y_out[t,r] = fl(float(acc[t,r]) * fl(x_scale[t] * w_scale[r]))
+ * with the int32 -> float32 conversion rounding to nearest even. block in
+ * {32, 64, 128, 256} with w_scale_count == rows * d / block: blockwise, the
+ * accumulator of every block kept apart,
+ *   y_out[t,r] = (...((0 + p_0) + p_1) + ...),
+ *   p_b = fl(float(acc_b[t,r]) * fl(x_scale[t] * w_scale[r * d / block + b]))
+ * in float32, blocks in ascending order, no FMA. acc_out is NULL or int32
+ * [n, rows] and receives acc; with blockwise scales it must be NULL. A NaN
+ * x_scale gives NaN outputs, which is no error.
+ *
+ * MFMA route: xq and w 16-byte aligned and d % 64 == 0 (d % 32 == 0 for block
+ * 32). v_mfma_i32_16x16x64_i8 with A = a 16-token tile of xq and B = a
+ * 16-channel tile of w, both contiguous along the reduction dimension: lane l
+ * holds the 16 consecutive bytes k = 16 (l >> 4) .. + 15 of row l & 15 of each
+ * (A and B share the assignment of k to lanes, so the sum does not depend on it);
+ * C / D is column (channel) l & 15, row (token) 4 (l >> 4) + register. I4 / I2
+ * fragments are 8 / 4 bytes unpacked and sign-extended in registers; no unpacked
+ * weight is written to memory. Block 32 uses v_mfma_i32_16x16x32_i8 with 8
+ * consecutive bytes per lane. A wave owns 64 tokens x 64 channels (4 x 4 MFMA
+ * tiles: 8 fragment loads feed 16 MFMAs, the next step's loads in flight), a
+ * workgroup 128 x 128. Generic route (every other d, e.g. odd d with packed
+ * weights whose rows begin inside a byte, and misaligned xq or w): one thread
+ * per output, one element at a time, the same bits.
+ *
+ * Refused before any launch: negative shapes, null xq / x_scale / w / w_scale /
+ * y_out, another w_kind, x_zero_point outside int8, block outside {0, 32, 64,
+ * 128, 256}, counts outside the sets above, acc_out with blockwise scales
+ * (MI355Q_BAD_ARG); a block that does not divide d (MI355Q_BAD_SHAPE,
+ * "Quantized dimension <d> is not divisible by block size <block>.");
+ * d > 65536 (MI355Q_UNSUPPORTED: d * 255 * 128 must stay below 2^31). After
+ * those n == 0 or rows == 0 enqueues nothing. workspace:
+ * mi355q_qfc_forward_workspace_bytes(rows, d, block) = 4 * rows * (block ? d /
+ * block : 1) rounded up to 256 bytes; it may be NULL when x_zero_point == 0.
+ *
+ * mi355q_sqdiff_cols_f64: a, b float32 [n, cols] row-major. Per column c
+ *   sq_diff_cols[c] = Sum_t (double(a[t,c]) - double(b[t,c]))^2
+ *   sq_b_cols[c]    = Sum_t double(b[t,c])^2
+ * in FLOAT64 and in a fixed order: strand p (of P = 4 * min(64, ceil(n / 256)))
+ * adds rows p, p + P, p + 2P, ... in ascending order, then a second kernel adds
+ * a column's P partials in index order; no floating-point atomics, the same bits
+ * in every run, |result - exact| <= n 2^-52 result. accumulate != 0 adds the
+ * sums onto what the outputs hold (the samples of a calibration set, in order);
+ * otherwise they are overwritten. cols == 0 enqueues nothing; n == 0 clears the
+ * outputs unless accumulate. workspace: mi355q_sqdiff_cols_workspace_bytes(n, cols).
+ * ------------------------------------------------------------------------ */
+int32_t mi355q_qfc_quantize_rows_f32(const float* x, int64_t n, int64_t d, int8_t* q_out, float* scale_out,
+                                     void* stream);
+size_t mi355q_qfc_forward_workspace_bytes(int64_t rows, int64_t d, int32_t block);
+int32_t mi355q_qfc_forward_i8(const int8_t* xq, int64_t n, int64_t d, const float* x_scale, int64_t x_scale_count,
+                              int32_t x_zero_point, const void* w, int32_t w_kind, int64_t rows, const float* w_scale,
+                              int64_t w_scale_count, int32_t block, float* y_out, int32_t* acc_out, void* workspace,
+                              size_t workspace_bytes, void* stream);
+size_t mi355q_sqdiff_cols_workspace_bytes(int64_t n, int64_t cols);
+int32_t mi355q_sqdiff_cols_f64(const float* a, const float* b, int64_t n, int64_t cols, double* sq_diff_cols,
+                               double* sq_b_cols, int32_t accumulate, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
