@@ -4,7 +4,8 @@
 //                           q = clamp(round_half_away_from_zero(fl(x * (127 / range))), -127, 127). The vector route
 //                           keeps the row in registers between the maximum and the rounding (one read of x), 16 floats
 //                           per lane and chunk, and stores 16 int8 at once; the scalar route reads the row twice.
-//   weight_sums_kernel      wsum[r][b] = Sum_k q_w[r][b * L + k] (int32, exact), the zero-point term of the accumulator.
+//   weight_sums_kernel      wsum[r][b] = Sum_k q_w[r][b * L + k] (int32, exact), the zero-point term of the accumulator
+//                           (qfc_frag.h, with the weight fragments: qfc16.hip uses both as well).
 //   qfc_mfma_kernel         acc = Xq W^^T on the int8 matrix cores. Both operands are contiguous along the reduction
 //                           dimension, so a lane's A fragment is 16 consecutive bytes of a row of Xq and its B fragment
 //                           16 consecutive elements of a row of W^ (8 bytes of int4, 4 bytes of int2, unpacked and
@@ -17,15 +18,15 @@
 //   sqdiff_cols_*_kernel    per column Sum_t (a - b)^2 and Sum_t b^2 in float64 in a fixed order.
 #include "common.h"
 #include "compare_target.h"
+#include "qfc_frag.h"
 
 namespace mi355q {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kQfcThreads;
 constexpr int kMaxD = 65536;           // d * 255 * 128 < 2^31
 constexpr int kVecMaxD = 16384;        // a row of the vector quantizer: 256 threads x 4 chunks x 16 floats
 
-using I32x4 = __attribute__((ext_vector_type(4))) int;
 struct __attribute__((aligned(16))) F4 { float x, y, z, w; };
 struct __attribute__((aligned(16))) U4 { uint32_t x, y, z, w; };
 
@@ -120,28 +121,6 @@ __global__ __launch_bounds__(kThreads) void quantize_rows_scalar_kernel(const fl
     qr[k] = rs.zero ? static_cast<int8_t>(0) : static_cast<int8_t>(round_away_clamp(xr[k] * rs.inv));
 }
 
-// ---------------------------------------------------------------- stored weight elements
-// element e of the flat weight (I4 / I2 packed over the whole tensor, element 0 in the low bits)
-__device__ __forceinline__ int weight_element(const uint8_t* w, int kind, long long e) {
-  if (kind == MI355Q_CMP_I8) return reinterpret_cast<const int8_t*>(w)[e];
-  if (kind == MI355Q_CMP_I4) return packed_element(w[e >> 1], 4, static_cast<int>(e & 1));
-  return packed_element(w[e >> 2], 2, static_cast<int>(e & 3));
-}
-
-// wsum[seg] = Sum of the `len` elements of segment seg (consecutive in the flat weight); W lanes per segment.
-template <int W>
-__global__ __launch_bounds__(kThreads) void weight_sums_kernel(const uint8_t* __restrict__ w, int kind, long long segments,
-                                                               long long len, int32_t* __restrict__ wsum) {
-  const long long seg = static_cast<long long>(blockIdx.x) * (kThreads / W) + threadIdx.x / W;
-  const int sub = threadIdx.x % W;
-  int s = 0;
-  if (seg < segments)
-    for (long long k = sub; k < len; k += W) s += weight_element(w, kind, seg * len + k);
-#pragma unroll
-  for (int off = W / 2; off > 0; off >>= 1) s += __shfl_xor(s, off, kWave);
-  if (seg < segments && sub == 0) wsum[seg] = s;
-}
-
 // ---------------------------------------------------------------- the integer product
 struct FwdArgs {
   const int8_t* xq;        // [n, d]
@@ -158,88 +137,6 @@ struct FwdArgs {
   int block;               // elements per block (d unless blockwise)
   int zp;
   int kind;
-};
-
-// 8 nibbles of a word -> two words of 4 sign-extended bytes each (nibble 0 in the low byte of the first)
-__device__ __forceinline__ void unpack_i4(uint32_t p, int& lo, int& hi) {
-  uint32_t e = p & 0x0F0F0F0Fu, o = (p >> 4) & 0x0F0F0F0Fu;       // nibbles 0,2,4,6 and 1,3,5,7
-  e |= (e & 0x08080808u) * 0x1Eu;                                 // 0x08 * 0x1E = 0xF0: sign bits, within the byte
-  o |= (o & 0x08080808u) * 0x1Eu;
-  lo = static_cast<int>((e & 0xFFu) | ((o & 0xFFu) << 8) | ((e & 0xFF00u) << 8) | ((o & 0xFF00u) << 16));
-  hi = static_cast<int>(((e >> 16) & 0xFFu) | (((o >> 16) & 0xFFu) << 8) | ((e >> 24) << 16) | ((o >> 24) << 24));
-}
-
-// 4 two-bit fields of a byte -> a word of 4 sign-extended bytes (field 0 in the low byte)
-__device__ __forceinline__ int unpack_i2(uint32_t b) {
-  uint32_t v = (b | (b << 6) | (b << 12) | (b << 18)) & 0x03030303u;
-  v |= (v & 0x02020202u) * 0x7Fu;                                 // 0x02 * 0x7F = 0xFE
-  return static_cast<int>(v);
-}
-
-template <int KSTEP> struct FragOf;
-template <> struct FragOf<64> { using T = I32x4; };
-template <> struct FragOf<32> { using T = long; };
-
-__device__ __forceinline__ long two_words(int lo, int hi) {
-  return static_cast<long>((static_cast<unsigned long>(static_cast<uint32_t>(hi)) << 32) | static_cast<uint32_t>(lo));
-}
-
-// The raw bytes of a lane's KSTEP / 4 consecutive weight elements at element offset e (a multiple of KSTEP / 4).
-template <int KIND, int KSTEP> struct RawW;
-template <> struct RawW<MI355Q_CMP_I8, 64> {
-  using T = I32x4;
-  static __device__ __forceinline__ T load(const uint8_t* w, long long e) { return *reinterpret_cast<const I32x4*>(w + e); }
-  static __device__ __forceinline__ T zero() { return I32x4{0, 0, 0, 0}; }
-  static __device__ __forceinline__ I32x4 unpack(T r) { return r; }
-};
-template <> struct RawW<MI355Q_CMP_I8, 32> {
-  using T = long;
-  static __device__ __forceinline__ T load(const uint8_t* w, long long e) { return *reinterpret_cast<const long*>(w + e); }
-  static __device__ __forceinline__ T zero() { return 0; }
-  static __device__ __forceinline__ long unpack(T r) { return r; }
-};
-template <> struct RawW<MI355Q_CMP_I4, 64> {
-  using T = unsigned long;
-  static __device__ __forceinline__ T load(const uint8_t* w, long long e) {
-    return *reinterpret_cast<const unsigned long*>(w + (e >> 1));
-  }
-  static __device__ __forceinline__ T zero() { return 0; }
-  static __device__ __forceinline__ I32x4 unpack(T r) {
-    int a, b, c, d;
-    unpack_i4(static_cast<uint32_t>(r), a, b);
-    unpack_i4(static_cast<uint32_t>(r >> 32), c, d);
-    return I32x4{a, b, c, d};
-  }
-};
-template <> struct RawW<MI355Q_CMP_I4, 32> {
-  using T = uint32_t;
-  static __device__ __forceinline__ T load(const uint8_t* w, long long e) {
-    return *reinterpret_cast<const uint32_t*>(w + (e >> 1));
-  }
-  static __device__ __forceinline__ T zero() { return 0; }
-  static __device__ __forceinline__ long unpack(T r) {
-    int a, b;
-    unpack_i4(r, a, b);
-    return two_words(a, b);
-  }
-};
-template <> struct RawW<MI355Q_CMP_I2, 64> {
-  using T = uint32_t;
-  static __device__ __forceinline__ T load(const uint8_t* w, long long e) {
-    return *reinterpret_cast<const uint32_t*>(w + (e >> 2));
-  }
-  static __device__ __forceinline__ T zero() { return 0; }
-  static __device__ __forceinline__ I32x4 unpack(T r) {
-    return I32x4{unpack_i2(r & 0xFFu), unpack_i2((r >> 8) & 0xFFu), unpack_i2((r >> 16) & 0xFFu), unpack_i2(r >> 24)};
-  }
-};
-template <> struct RawW<MI355Q_CMP_I2, 32> {
-  using T = uint16_t;
-  static __device__ __forceinline__ T load(const uint8_t* w, long long e) {
-    return *reinterpret_cast<const uint16_t*>(w + (e >> 2));
-  }
-  static __device__ __forceinline__ T zero() { return 0; }
-  static __device__ __forceinline__ long unpack(T r) { return two_words(unpack_i2(r & 0xFFu), unpack_i2(r >> 8)); }
 };
 
 template <int KSTEP> struct XFrag;
@@ -559,19 +456,9 @@ extern "C" int32_t mi355q_qfc_forward_i8(const int8_t* xq, int64_t n, int64_t d,
   hipStream_t st = as_stream(stream);
 
   if (x_zero_point != 0) {
-    const long long segments = rows * g.nblocks;
-    if (g.block <= 256) {
-      const long long blocks = (segments + kThreads / 8 - 1) / (kThreads / 8);
-      if (blocks > 0x7FFFFFFFLL) return fail(MI355Q_UNSUPPORTED, "too many weight blocks for one launch");
-      hipLaunchKernelGGL(weight_sums_kernel<8>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, st, g.w, w_kind,
-                         segments, static_cast<long long>(g.block), static_cast<int32_t*>(workspace));
-    } else {
-      const long long blocks = (segments + kThreads / kWave - 1) / (kThreads / kWave);
-      if (blocks > 0x7FFFFFFFLL) return fail(MI355Q_UNSUPPORTED, "too many weight blocks for one launch");
-      hipLaunchKernelGGL(weight_sums_kernel<kWave>, dim3(static_cast<unsigned>(blocks)), dim3(kThreads), 0, st, g.w, w_kind,
-                         segments, static_cast<long long>(g.block), static_cast<int32_t*>(workspace));
-    }
-    MI355Q_CHECK_LAUNCH("weight sums launch");
+    const int32_t st_sums = launch_weight_sums(g.w, w_kind, rows * g.nblocks, static_cast<long long>(g.block),
+                                               static_cast<int32_t*>(workspace), st);
+    if (st_sums != MI355Q_OK) return st_sums;
   }
 
   const int kstep = blockwise && block == 32 ? 32 : 64;

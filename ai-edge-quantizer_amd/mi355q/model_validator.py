@@ -877,6 +877,19 @@ class LayerExecutionKernels:
     from . import ops
     return ops.qfc_forward(xq, x_scale, x_zero_point, target, rows, d)
 
+  def quantize_static16(self, x, scale: float):
+    """(q int16 [n, d], its one scale): q = clip(rint(x / s_x), -32768, 32767), symmetric, ops.quantize as it stands."""
+    import torch
+    from . import ops
+    from . import runtime as rt
+    s = torch.tensor([scale], dtype=torch.float32, device=rt.device())
+    zp = torch.tensor([0], dtype=torch.int32, device=rt.device())
+    return ops.quantize(x.contiguous(), 1, 1, x.numel(), s, zp, 16, False), s
+
+  def forward16(self, xq, x_scale, target, rows: int, d: int):
+    from . import ops
+    return ops.qfc_forward_i16(xq, x_scale, target, rows, d)
+
   def sqdiff(self, yq, y, sums):
     """(Sum_t (yq - y)^2, Sum_t y^2) per column, added onto `sums` (None: the first chunk)."""
     from . import ops
@@ -890,7 +903,8 @@ class LayerExecutionComparison(LayerOutputComparison):
   """Per FULLY_CONNECTED op (keyed by its output tensor's name): how far the quantized op's integer execution is
   from the float product over the calibration samples. `results[name]` holds `weight`, `input`, `rows`, `d`,
   `tokens`, `mode` ("static", "dynamic" or "weight_only"), `signal`, `error`, `output_mse`, `output_snr` and
-  `per_channel_error` (float64 [rows]), with `follow_input_transforms` also `input_transform` and `hadamard_size`;
+  `per_channel_error` (float64 [rows]), with `follow_input_transforms` also `input_transform` and `hadamard_size`,
+  with `int16_activations` also `activation_bits` (8, 16, or None for dynamic and weight-only ops);
   `skipped[name]` is the reason an op was not computed."""
 
   def save(self, save_folder: str, model_name: str) -> str:
@@ -906,7 +920,8 @@ class LayerExecutionComparison(LayerOutputComparison):
 def compare_layer_execution(reference_model, target_model, samples: Iterable[dict],
                             signature_key: Optional[str] = DEFAULT_SIGNATURE_KEY, *,
                             kernels: Optional[LayerExecutionKernels] = None,
-                            follow_input_transforms: bool = False) -> LayerExecutionComparison:
+                            follow_input_transforms: bool = False,
+                            int16_activations: bool = False) -> LayerExecutionComparison:
   """Executes every quantized FULLY_CONNECTED op in integers on the calibration samples and compares it with the
   float model's product, for every op of the float model with a constant 2-D float32 weight [rows, d] whose input 0
   is in `samples` (the {tensor name: array or device tensor} maps calibrate() takes; tensors of any rank are rows of
@@ -931,6 +946,14 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
   unless `follow_input_transforms` is set. Then X goes through the inserted op's own constant first
   (ops.hadamard_rotate, or the multiply; _input_transform) and the comparison is still against the float model's
   product of the untransformed input; every entry then also carries `input_transform` and `hadamard_size`.
+
+  With `int16_activations` an op whose input 0 is INT16 (the a16w8 models of static_wi8_ai16) is executed as well,
+  with mode "static": the tensor must have one scale, a zero point that is 0 or absent (INT16 activations are
+  symmetric), and be a QUANTIZE of the float model's input or that input itself, in front of the integer weight
+  itself; anything else about it is "the quantized op reads a transformed input". Then
+  q = clip(rint(x / s_x), -32768, 32767) (ops.quantize, 16 bits), acc = Sum_k q q_w is exact in int64 and
+  Yq = float32(float64(acc) * float64(s_x * s_w)) (ops.qfc_forward_i16), and every entry also carries
+  `activation_bits`: 16, 8 for an INT8 activation, None for dynamic and weight-only ops.
   """
   kernels = kernels or LayerExecutionKernels()
   samples = list(samples)
@@ -978,12 +1001,13 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
       continue
     # ---- the activation it reads
     x_in = tgt_sg.tensors[fc.inputs[0]]
-    if x_in.type == schema.TensorType.INT16:
+    if x_in.type == schema.TensorType.INT16 and not int16_activations:
       out.skipped[y_name] = SKIP_INT16
       continue
     transform = (TRANSFORM_NONE, None, 0)
     x_quant = None
-    if x_in.type == schema.TensorType.INT8:
+    activation_bits = None
+    if x_in.type in (schema.TensorType.INT8, schema.TensorType.INT16):
       q = x_in.quantization
       source = name(fc.inputs[0])
       quantize = producers.get(int(fc.inputs[0]))
@@ -993,6 +1017,10 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
         out.skipped[y_name] = SKIP_INPUT
         continue
       zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
+      activation_bits = 16 if x_in.type == schema.TensorType.INT16 else 8
+      if activation_bits == 16 and zero_point != 0:
+        out.skipped[y_name] = SKIP_INPUT
+        continue
       x_quant = (float(np.float32(q.scale[0])), zero_point)
       mode = MODE_STATIC
     elif x_in.type == schema.TensorType.FLOAT32:
@@ -1042,6 +1070,9 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
         elif mode == MODE_DYNAMIC:
           xq, x_scale = kernels.quantize_dynamic(xt)
           yq = kernels.forward(xq, x_scale, 0, t_dev, rows, d)
+        elif activation_bits == 16:
+          xq, x_scale = kernels.quantize_static16(xt, x_quant[0])
+          yq = kernels.forward16(xq, x_scale, t_dev, rows, d)
         else:
           xq, x_scale = kernels.quantize_static(xt, *x_quant)
           yq = kernels.forward(xq, x_scale, x_quant[1], t_dev, rows, d)
@@ -1059,6 +1090,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                            "output_snr": (signal / rows) / (mse + 1e-9), "per_channel_error": per_channel}
     if follow_input_transforms:
       out.results[y_name].update(input_transform=transform[0], hadamard_size=transform[2])
+    if int16_activations:
+      out.results[y_name]["activation_bits"] = activation_bits
   return out
 
 

@@ -1055,22 +1055,14 @@ def qfc_quantize_rows(x2d: torch.Tensor):
   return q, scale
 
 
-def qfc_forward(xq: torch.Tensor, x_scale: torch.Tensor, x_zero_point: int, target: CompareTarget, rows: int, d: int,
-                want_acc: bool = False):
-  """The integer FULLY_CONNECTED product of int8 activations xq [n, d] and the stored integer weight [rows, d] of
-  `target` (kind i8 / i4 / i2, as the validators build it), rescaled to float32 [n, rows]:
-  y = float(Sum_k (xq - x_zero_point) q_w) * (x_scale * w_scale), with one int32 accumulator per block under
-  blockwise scales (added in float32 in ascending order). The pre-bias product: bias, fused activation and the
-  requantization of the output do not enter. `x_scale` holds 1 or n float32 entries. The scale view of `target`
-  decides the granularity: channels = 1 per tensor; channels = rows with inner = d per channel; inner = a block size
-  blockwise. Returns y, or (y, acc int32 [n, rows]) with `want_acc` (not with blockwise scales). Does not
-  synchronize."""
-  rt.require_gpu()
+def _qfc_block(who: str, xq: torch.Tensor, dtype, target: CompareTarget, rows: int, d: int) -> int:
+  """The argument checks qfc_forward and qfc_forward_i16 share; returns the block size the scale view means (0: per
+  tensor or per channel)."""
   if target.kind not in ("i8", "i4", "i2"):
-    raise ValueError(f"qfc_forward needs an i8 / i4 / i2 weight, got {target.kind!r}")
-  rows, d = int(rows), int(d)
-  if xq.dtype != torch.int8 or not xq.is_cuda or xq.dim() != 2 or xq.shape[1] != d:
-    raise TypeError(f"expected an int8 [n, {d}] device tensor, got {xq.dtype} {tuple(xq.shape)} on {xq.device}")
+    raise ValueError(f"{who} needs an i8 / i4 / i2 weight, got {target.kind!r}")
+  if xq.dtype != dtype or not xq.is_cuda or xq.dim() != 2 or xq.shape[1] != d:
+    name = str(dtype).replace("torch.", "")
+    raise TypeError(f"expected an {name} [n, {d}] device tensor, got {xq.dtype} {tuple(xq.shape)} on {xq.device}")
   if target.n != rows * d:
     raise ValueError(f"the weight has {target.n} elements, expected {rows} x {d}")
   if target.zero_point is not None and bool(torch.any(target.zero_point != 0)):
@@ -1086,6 +1078,22 @@ def qfc_forward(xq: torch.Tensor, x_scale: torch.Tensor, x_zero_point: int, targ
                      f" nor blockwise over a [{rows}, {d}] weight")
   if target.scale.numel() != target.channels:
     raise ValueError("scale must have one entry per channel")
+  return block
+
+
+def qfc_forward(xq: torch.Tensor, x_scale: torch.Tensor, x_zero_point: int, target: CompareTarget, rows: int, d: int,
+                want_acc: bool = False):
+  """The integer FULLY_CONNECTED product of int8 activations xq [n, d] and the stored integer weight [rows, d] of
+  `target` (kind i8 / i4 / i2, as the validators build it), rescaled to float32 [n, rows]:
+  y = float(Sum_k (xq - x_zero_point) q_w) * (x_scale * w_scale), with one int32 accumulator per block under
+  blockwise scales (added in float32 in ascending order). The pre-bias product: bias, fused activation and the
+  requantization of the output do not enter. `x_scale` holds 1 or n float32 entries. The scale view of `target`
+  decides the granularity: channels = 1 per tensor; channels = rows with inner = d per channel; inner = a block size
+  blockwise. Returns y, or (y, acc int32 [n, rows]) with `want_acc` (not with blockwise scales). Does not
+  synchronize."""
+  rt.require_gpu()
+  rows, d = int(rows), int(d)
+  block = _qfc_block("qfc_forward", xq, torch.int8, target, rows, d)
   # (no .contiguous(): a misaligned view is still dense, and the library routes on the address)
   n = xq.shape[0]
   x_scale = _f32(x_scale).view(-1)
@@ -1100,6 +1108,32 @@ def qfc_forward(xq: torch.Tensor, x_scale: torch.Tensor, x_zero_point: int, targ
                                      rt.ptr(target.data), COMPARE_KINDS[target.kind], rows, rt.ptr(target.scale),
                                      target.scale.numel(), block, rt.ptr(y), rt.ptr(acc), rt.ptr(ws), nbytes,
                                      rt.stream_ptr()))
+  return (y, acc) if want_acc else y
+
+
+def qfc_forward_i16(xq: torch.Tensor, x_scale: torch.Tensor, target: CompareTarget, rows: int, d: int,
+                    want_acc: bool = False):
+  """The integer FULLY_CONNECTED product of int16 activations xq [n, d] (symmetric: no zero point) and the stored
+  integer weight [rows, d] of `target`, as qfc_forward reads it: acc = Sum_k xq q_w exact in int64 and
+  y = float32(float64(acc) * float64(x_scale * w_scale)), the scale product in float32; with blockwise scales one
+  exact accumulator per block, rescaled so and added in float32 in ascending order (include/mi355q.h, "Integer
+  execution, int16 activations"). `x_scale` holds 1 or n float32 entries. Returns y float32 [n, rows], or
+  (y, acc int64 [n, rows]) with `want_acc` (not with blockwise scales). Does not synchronize."""
+  rt.require_gpu()
+  rows, d = int(rows), int(d)
+  block = _qfc_block("qfc_forward_i16", xq, torch.int16, target, rows, d)
+  n = xq.shape[0]
+  x_scale = _f32(x_scale).view(-1)
+  y = rt.empty((n, rows), torch.float32)
+  acc = rt.empty((n, rows), torch.int64) if want_acc else None
+  L = _ffi.lib()
+  nbytes = L.mi355q_qfc_forward_i16_workspace_bytes(rows, d, block)
+  ws = rt.empty((max(nbytes, 1),), torch.uint8)
+  if not xq.is_contiguous():
+    xq = xq.contiguous()
+  _ffi.check(L.mi355q_qfc_forward_i16(rt.ptr(xq), n, d, rt.ptr(x_scale), x_scale.numel(), rt.ptr(target.data),
+                                      COMPARE_KINDS[target.kind], rows, rt.ptr(target.scale), target.scale.numel(),
+                                      block, rt.ptr(y), rt.ptr(acc), rt.ptr(ws), nbytes, rt.stream_ptr()))
   return (y, acc) if want_acc else y
 
 

@@ -996,6 +996,62 @@ int32_t mi355q_sqdiff_cols_f64(const float* a, const float* b, int64_t n, int64_
                                double* sq_b_cols, int32_t accumulate, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Integer execution, int16 activations (csrc/qfc16.hip): the FULLY_CONNECTED op
+ * of an a16w8 model (static_wi8_ai16). The arithmetic is this library's own
+ * definition.
+ *
+ * mi355q_qfc_forward_i16: xq is int16 [n, d] over the full range -32768 ..
+ * 32767 with NO zero point (INT16 activations are symmetric); w, w_kind, rows,
+ * w_scale, w_scale_count, block, x_scale and x_scale_count are as for
+ * mi355q_qfc_forward_i8 (weight zero points 0).
+ *   acc[t,r] = Sum_k xq[t,k] * w[r,k]                          (int64, exact)
+ *   y_out[t,r] = fl32( double(acc[t,r]) * double( fl32(x_scale[t] * w_scale[r]) ) )
+ * The scale product is rounded to float32; the accumulator (up to 39 bits) goes
+ * through float64, where it is exact, so the rescale adds one float64 and one
+ * float32 rounding and no float32 rounding of the integer itself. In NumPy:
+ *   sc = xs[:, None] * sw[None, :]                              (float32)
+ *   y = (acc.astype(np.float64) * sc.astype(np.float64)).astype(np.float32)
+ * Blockwise (block in {32, 64, 128, 256}, w_scale_count == rows * d / block):
+ * one exact accumulator per block,
+ *   p_b = fl32( double(acc_b[t,r]) * double( fl32(x_scale[t] * w_scale[r * d / block + b]) ) )
+ *   y_out[t,r] = (...((0 + p_0) + p_1) + ...)
+ * in float32, blocks in ascending order, no FMA (the i8 entry's rule). acc_out
+ * is NULL or int64 [n, rows]; with blockwise scales it must be NULL. A NaN
+ * x_scale gives NaN outputs, which is no error.
+ *
+ * MFMA route (xq and w 16-byte aligned, d % 64 == 0, or d % 32 == 0 for block
+ * 32): gfx950 has no int16 matrix instruction, so with h = x >> 8 (arithmetic,
+ * -128 .. 127), l_u = x & 255 and l_s = int8(l_u ^ 0x80) = l_u - 128
+ *   acc = 256 * Sum_k h w + Sum_k l_s w + 128 * Sum_k w[r,k]
+ * The first two sums are int32-exact for d <= 65536 (each within 65536 * 128 *
+ * 128 = 2^30) and run on v_mfma_i32_16x16x64_i8 (v_mfma_i32_16x16x32_i8 for
+ * block 32); the third is the weight-sums kernel's, per row or per block, into
+ * `workspace`; the three are combined in int64 in the epilogue. A lane's A
+ * fragment is 16 consecutive int16 of a row of xq (two 16-byte loads), split
+ * into the high-byte and the biased low-byte fragment in registers (v_perm_b32);
+ * the B fragment is the i8 entry's, read and unpacked once per step for both
+ * planes. Lane, row / column and C / D maps are the i8 entry's. A wave owns 32
+ * tokens x 64 channels (2 x 4 MFMA tiles in two planes: 6 fragment loads feed
+ * 16 MFMAs), a workgroup 64 x 128. Generic route (every other d or alignment):
+ * one thread per output with an int64 accumulator, the same bits.
+ *
+ * Refused before any launch, with the i8 entry's texts: negative shapes, null
+ * xq / x_scale / w / w_scale / y_out, another w_kind, block outside {0, 32, 64,
+ * 128, 256}, counts outside the sets above, acc_out with blockwise scales
+ * (MI355Q_BAD_ARG); a block that does not divide d (MI355Q_BAD_SHAPE); d > 65536
+ * (MI355Q_UNSUPPORTED: the int32 planes); a workspace that is NULL or smaller
+ * than mi355q_qfc_forward_i16_workspace_bytes(rows, d, block) = 4 * rows *
+ * (block ? d / block : 1) rounded up to 256 bytes (MI355Q_BAD_ARG; the weight
+ * sums are a term of every accumulator, so it is always required). After those
+ * n == 0 or rows == 0 enqueues nothing.
+ * ------------------------------------------------------------------------ */
+size_t mi355q_qfc_forward_i16_workspace_bytes(int64_t rows, int64_t d, int32_t block);
+int32_t mi355q_qfc_forward_i16(const int16_t* xq, int64_t n, int64_t d, const float* x_scale, int64_t x_scale_count,
+                               const void* w, int32_t w_kind, int64_t rows, const float* w_scale, int64_t w_scale_count,
+                               int32_t block, float* y_out, int64_t* acc_out, void* workspace, size_t workspace_bytes,
+                               void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
