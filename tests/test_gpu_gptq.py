@@ -3,7 +3,8 @@
 Tolerance class T2: the reference runs sgemm / LAPACK whose add
 order is unspecified. What is exact and tested as such: the apply step given the
 reference's own Hinv when d <= 64 (no GEMM involved), and the reference's
-known-answer vectors."""
+known-answer vectors. Every route of the Hessian inverse is also held bit for bit to
+Hessians with an exact inverse: test_gpu_hinv_routes.py."""
 import warnings
 
 import numpy as np

@@ -24,7 +24,8 @@ agreement with oracle.aeq_oracle.gptq_apply where the oracle can express the cas
 route, and the argument checks of both entry points.
 
 What this file does NOT cover: non-finite weights or scales; targets of 26 bits and more (the clip bound itself rounds
-there); the Hessian and its inverse; speed. Hinv on this data has two significant bits and the errors few (about 20
+there); the Hessian and its inverse (every route of the inverse, bit for bit on exact Hessians:
+test_gpu_hinv_routes.py); speed. Hinv on this data has two significant bits and the errors few (about 20
 in the 4-bit 4096-column case, whose scales grow along the row), so the low planes of Hinv in the bf16x3 split are
 empty: the test proves upd_bf16x3's tiling, indexing and accumulation, not that the split of a full-mantissa value is
 exact -- the rate-based full-size tests of test_gpu_gptq.py stay for that.
