@@ -816,6 +816,92 @@ SKIP_NO_SAMPLE = "no sample for the input"
 SKIP_SAMPLE_SHAPE = "the sample's size is no multiple of the weight's reduction dimension"
 SKIP_KIND = "the target weight is neither int8, int4 nor int2"
 EXECUTION_CHUNK_ROWS = 4096
+# `quantized_outputs`: why an executed static op has no final_* figures
+FINAL_SKIP_OUTPUT = "the output tensor is not INT8 / INT16 (as the activation is) with one scale and no INT16 zero point"
+FINAL_SKIP_BIAS = "the bias is no constant INT32 / INT64 vector of rows entries"
+FINAL_SKIP_BIAS_RANGE = "the INT64 bias is beyond +-2^47"
+FINAL_SKIP_FLOAT_BIAS = "the float model's bias is no constant float32 vector of rows entries"
+FINAL_SKIP_ACTIVATION = "the fused activation is none of NONE, RELU, RELU_N1_TO_1 and RELU6"
+FINAL_SKIP_WEIGHTS_FORMAT = "weightsFormat is not DEFAULT"
+FINAL_SKIP_MULTIPLIER = "s_x s_w / s_y has no fixed-point multiplier within the op's shift range"
+
+
+@dataclasses.dataclass
+class OutputPlan:
+  """What the integer epilogue of one static FULLY_CONNECTED op needs, read from the two models."""
+  bits: int                          # 8 or 16
+  bias: Optional[np.ndarray]         # int32 / int64 [rows] of the target op, or None
+  float_bias: Optional[np.ndarray]   # float32 [rows] of the float op, or None
+  multiplier: np.ndarray             # int32, 1 or rows entries
+  shift: np.ndarray
+  scale: float                       # s_y
+  zero_point: int                    # zp_y
+  act_min: int
+  act_max: int
+  fused: int                         # the target op's fused activation
+  float_fused: int                   # the float op's
+
+
+def _fc_option(op, field: str) -> int:
+  return int(getattr(op.builtinOptions, field, 0) or 0) if op.builtinOptions is not None else 0
+
+
+def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray):
+  """An OutputPlan, or the FINAL_SKIP_* reason there is none."""
+  from . import ops
+  if _fc_option(fc, "weightsFormat") != 0 or _fc_option(ref_op, "weightsFormat") != 0:
+    return FINAL_SKIP_WEIGHTS_FORMAT
+  fused, float_fused = _fc_option(fc, "fusedActivationFunction"), _fc_option(ref_op, "fusedActivationFunction")
+  if fused not in ops.FUSED_ACTIVATION_NAMES or float_fused not in ops.FUSED_ACTIVATION_NAMES:
+    return FINAL_SKIP_ACTIVATION
+  # ---- the output tensor
+  y = tgt_sg.tensors[fc.outputs[0]]
+  q = y.quantization
+  want = schema.TensorType.INT16 if bits == 16 else schema.TensorType.INT8
+  if y.type != want or q is None or q.scale is None or len(q.scale) != 1:
+    return FINAL_SKIP_OUTPUT
+  zp_y = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
+  if (bits == 16 and zp_y != 0) or not -128 <= zp_y <= 127:
+    return FINAL_SKIP_OUTPUT
+  s_y = float(np.float32(q.scale[0]))
+  if not (np.isfinite(s_y) and s_y > 0):
+    return FINAL_SKIP_OUTPUT
+  # ---- the two biases
+  def constant(m, sg, op, ttype) -> Any:
+    """The op's input 2 as a flat array of `ttype`, None when absent, False when it is something else."""
+    if len(op.inputs) < 3 or op.inputs[2] < 0:
+      return None
+    t = sg.tensors[op.inputs[2]]
+    if t.type != ttype or not _has_data(m.buffers, t) or _numel(t) != rows:
+      return False
+    return np.ascontiguousarray(_raw_bytes(m.buffers, t)).view(schema.NUMPY_DTYPE[ttype])[:rows].copy()
+  bias = constant(tgt, tgt_sg, fc, schema.TensorType.INT64 if bits == 16 else schema.TensorType.INT32)
+  if bias is False:
+    return FINAL_SKIP_BIAS
+  if bits == 16 and bias is not None and np.any((bias < -(1 << 47)) | (bias > (1 << 47))):
+    return FINAL_SKIP_BIAS_RANGE
+  float_bias = constant(ref, ref_sg, ref_op, schema.TensorType.FLOAT32)
+  if float_bias is False:
+    return FINAL_SKIP_FLOAT_BIAS
+  # ---- multipliers, in float64 from the float32 scales as they are stored
+  w_scale = np.asarray(w_scale, np.float32).reshape(-1)
+  if w_scale.size not in (1, rows):
+    return FINAL_SKIP_MULTIPLIER
+  lo, hi = ops.QFC_SHIFT_RANGE[bits]
+  multiplier, shift = [], []
+  for s_w in w_scale.tolist():
+    real = float(np.float32(s_x)) * float(s_w) / s_y
+    try:
+      m_r, e_r = ops.quantize_multiplier(real)
+    except ValueError:
+      return FINAL_SKIP_MULTIPLIER
+    if not lo <= e_r <= hi:
+      return FINAL_SKIP_MULTIPLIER
+    multiplier.append(m_r)
+    shift.append(e_r)
+  act_min, act_max = ops.activation_range(fused, s_y, zp_y, bits)
+  return OutputPlan(bits, bias, float_bias, np.asarray(multiplier, np.int32), np.asarray(shift, np.int32), s_y, zp_y,
+                    act_min, act_max, fused, float_fused)
 
 
 class LayerExecutionKernels:
@@ -890,6 +976,45 @@ class LayerExecutionKernels:
     from . import ops
     return ops.qfc_forward_i16(xq, x_scale, target, rows, d)
 
+  def bias(self, values: np.ndarray):
+    """A bias vector (int32, int64 or float32 [rows]) where the kernels read it."""
+    from . import runtime as rt
+    return rt.to_device(np.ascontiguousarray(values))
+
+  def output(self, xq, x_zero_point: int, target, rows: int, d: int, bias, multiplier, shift, out_zero_point: int,
+             act_min: int, act_max: int):
+    """int8 [n, rows]: what the static int8 op stores (ops.qfc_output)."""
+    from . import ops
+    return ops.qfc_output(xq, x_zero_point, target, rows, d, bias, multiplier, shift, out_zero_point, act_min, act_max)
+
+  def output16(self, xq, target, rows: int, d: int, bias, multiplier, shift, act_min: int, act_max: int):
+    """int16 [n, rows]: what the static int16-activation op stores (ops.qfc_output_i16)."""
+    from . import ops
+    return ops.qfc_output_i16(xq, target, rows, d, bias, multiplier, shift, act_min, act_max)
+
+  def dequantize_output(self, q, scale: float, zero_point: int):
+    """float32 [n, rows] = float32(q - zp_y) * s_y (ops.dequantize; the difference fits int16 for both types)."""
+    import torch
+    from . import ops
+    from . import runtime as rt
+    s = torch.tensor([scale], dtype=torch.float32, device=rt.device())
+    zp = torch.tensor([zero_point], dtype=torch.int32, device=rt.device())
+    return ops.dequantize(q, 1, 1, q.numel(), s, zp, 16)
+
+  def reference_output(self, y, bias, fused: int):
+    """float32 [n, rows] = act(y + b) of the float op: one float32 addition, then the activation's clamp."""
+    import torch
+    from . import ops
+    if bias is not None:
+      y = y + bias
+    if fused == ops.FUSED_RELU:
+      return torch.clamp(y, min=0.0)
+    if fused == ops.FUSED_RELU6:
+      return torch.clamp(y, min=0.0, max=6.0)
+    if fused == ops.FUSED_RELU_N1_TO_1:
+      return torch.clamp(y, min=-1.0, max=1.0)
+    return y
+
   def sqdiff(self, yq, y, sums):
     """(Sum_t (yq - y)^2, Sum_t y^2) per column, added onto `sums` (None: the first chunk)."""
     from . import ops
@@ -905,7 +1030,16 @@ class LayerExecutionComparison(LayerOutputComparison):
   `tokens`, `mode` ("static", "dynamic" or "weight_only"), `signal`, `error`, `output_mse`, `output_snr` and
   `per_channel_error` (float64 [rows]), with `follow_input_transforms` also `input_transform` and `hadamard_size`,
   with `int16_activations` also `activation_bits` (8, 16, or None for dynamic and weight-only ops);
+  with `quantized_outputs` also `output_bits` and, for a static op executed through to its stored output,
+  `fused_activation`, `final_signal`, `final_error`, `final_output_mse`, `final_output_snr` and
+  `final_per_channel_error`, or `final_skipped` with the reason there are none;
   `skipped[name]` is the reason an op was not computed."""
+
+  def as_dict(self) -> dict:
+    out = super().as_dict()
+    for entry in out["layers"].values():
+      entry.pop("final_per_channel_error", None)
+    return out
 
   def save(self, save_folder: str, model_name: str) -> str:
     """`<model_name>_layer_execution_errors.json`, without the per-channel arrays."""
@@ -921,7 +1055,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                             signature_key: Optional[str] = DEFAULT_SIGNATURE_KEY, *,
                             kernels: Optional[LayerExecutionKernels] = None,
                             follow_input_transforms: bool = False,
-                            int16_activations: bool = False) -> LayerExecutionComparison:
+                            int16_activations: bool = False,
+                            quantized_outputs: bool = False) -> LayerExecutionComparison:
   """Executes every quantized FULLY_CONNECTED op in integers on the calibration samples and compares it with the
   float model's product, for every op of the float model with a constant 2-D float32 weight [rows, d] whose input 0
   is in `samples` (the {tensor name: array or device tensor} maps calibrate() takes; tensors of any rank are rows of
@@ -954,6 +1089,21 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
   q = clip(rint(x / s_x), -32768, 32767) (ops.quantize, 16 bits), acc = Sum_k q q_w is exact in int64 and
   Yq = float32(float64(acc) * float64(s_x * s_w)) (ops.qfc_forward_i16), and every entry also carries
   `activation_bits`: 16, 8 for an INT8 activation, None for dynamic and weight-only ops.
+
+  With `quantized_outputs` a static op is also executed THROUGH TO ITS STORED OUTPUT, the one tensor the next op
+  reads: q_out = clamp(requantize(acc + bias) + zp_y, act_min, act_max) in integers (ops.qfc_output /
+  ops.qfc_output_i16: the int32 / int64 bias constant of the op, the fixed-point multiplier of
+  double(s_x) double(s_w[r]) / double(s_y) per channel from ops.quantize_multiplier, the output tensor's own
+  (s_y, zp_y), the fused activation's integer range from ops.activation_range), Yq = s_y (q_out - zp_y)
+  (ops.dequantize), and Y = act(X W^T + b) in float32 from the FLOAT model's own bias and fused activation. Every
+  entry then carries `output_bits` (8, 16, or None for dynamic and weight-only ops), and an op executed so
+  `fused_activation` (the name), `final_signal`, `final_error`, `final_output_mse`, `final_output_snr` and
+  `final_per_channel_error`, formed from Yq and Y as the keys without the prefix are. It needs: an INT8 (INT16 under
+  16-bit activations, zero point 0 or absent) output tensor with one scale; a bias that is absent or a constant
+  INT32 (INT64, within +-2^47) vector of rows entries; a float bias that is absent or a constant float32 vector; a
+  fused activation NONE, RELU, RELU_N1_TO_1 or RELU6; weightsFormat DEFAULT; multipliers within the op's shift range.
+  Otherwise the pre-bias figures stay and the entry carries `final_skipped` (a FINAL_SKIP_* reason) and no final_*
+  figure. Without the keyword nothing changes.
   """
   kernels = kernels or LayerExecutionKernels()
   samples = list(samples)
@@ -974,7 +1124,7 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
     return schema.tensor_name(tgt_sg.tensors[index]) if index is not None and index >= 0 else None
 
   out = LayerExecutionComparison(signature_key)
-  for _, x_name, w, y_name in _fully_connected_ops(ref, sg_ref):
+  for ref_op, x_name, w, y_name in _fully_connected_ops(ref, sg_ref):
     w_name = schema.tensor_name(w)
     if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 2):
       out.skipped[y_name] = SKIP_WEIGHT
@@ -1057,6 +1207,13 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
     w_dev = kernels.weight(values, rows, d)
     t_dev = kernels.target(plan)
     dq_dev = kernels.dequantized(t_dev, rows, d) if mode == MODE_WEIGHT_ONLY else None
+    final, final_sums, bias_dev, float_bias_dev = None, None, None, None
+    if quantized_outputs and mode == MODE_STATIC:
+      final = _output_plan(ref, ref.subgraphs[sg_ref], ref_op, tgt, tgt_sg, fc, rows, activation_bits, x_quant[0],
+                           plan.scale)
+    if isinstance(final, OutputPlan):
+      bias_dev = None if final.bias is None else kernels.bias(final.bias)
+      float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
     sums, tokens = None, 0
     for value in present:
       x = kernels.sample(value, d)
@@ -1077,6 +1234,15 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
           xq, x_scale = kernels.quantize_static(xt, *x_quant)
           yq = kernels.forward(xq, x_scale, x_quant[1], t_dev, rows, d)
         sums = kernels.sqdiff(yq, y, sums)
+        if isinstance(final, OutputPlan):
+          if activation_bits == 16:
+            q_out = kernels.output16(xq, t_dev, rows, d, bias_dev, final.multiplier, final.shift, final.act_min,
+                                     final.act_max)
+          else:
+            q_out = kernels.output(xq, x_quant[1], t_dev, rows, d, bias_dev, final.multiplier, final.shift,
+                                   final.zero_point, final.act_min, final.act_max)
+          final_sums = kernels.sqdiff(kernels.dequantize_output(q_out, final.scale, final.zero_point),
+                                      kernels.reference_output(y, float_bias_dev, final.float_fused), final_sums)
       tokens += n
     if sums is None:          # (every sample of the input was empty)
       out.skipped[y_name] = SKIP_NO_SAMPLE
@@ -1092,6 +1258,20 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
       out.results[y_name].update(input_transform=transform[0], hadamard_size=transform[2])
     if int16_activations:
       out.results[y_name]["activation_bits"] = activation_bits
+    if quantized_outputs:
+      entry = out.results[y_name]
+      entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
+      if isinstance(final, OutputPlan):
+        from . import ops
+        f_diff, f_ref = kernels.host(final_sums)
+        f_channel = np.asarray(f_diff, np.float64) / tokens
+        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
+        f_mse = f_error / rows
+        entry.update(fused_activation=ops.FUSED_ACTIVATION_NAMES[final.fused], final_signal=f_signal,
+                     final_error=f_error, final_output_mse=f_mse, final_output_snr=(f_signal / rows) / (f_mse + 1e-9),
+                     final_per_channel_error=f_channel)
+      elif final is not None:
+        entry["final_skipped"] = final
   return out
 
 

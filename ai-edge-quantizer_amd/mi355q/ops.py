@@ -8,6 +8,7 @@ include/mi355q.h.
 from __future__ import annotations
 
 import contextlib as _contextlib
+import math
 import os
 import threading
 
@@ -1135,6 +1136,152 @@ def qfc_forward_i16(xq: torch.Tensor, x_scale: torch.Tensor, target: CompareTarg
                                       COMPARE_KINDS[target.kind], rows, rt.ptr(target.scale), target.scale.numel(),
                                       block, rt.ptr(y), rt.ptr(acc), rt.ptr(ws), nbytes, rt.stream_ptr()))
   return (y, acc) if want_acc else y
+
+
+# (include/mi355q.h, "Integer execution, through to the stored output")
+FUSED_NONE, FUSED_RELU, FUSED_RELU_N1_TO_1, FUSED_RELU6 = 0, 1, 2, 3
+FUSED_ACTIVATION_NAMES = {FUSED_NONE: "NONE", FUSED_RELU: "RELU", FUSED_RELU_N1_TO_1: "RELU_N1_TO_1", FUSED_RELU6: "RELU6"}
+QFC_SHIFT_RANGE = {8: (-31, 30), 16: (-31, 14)}
+
+
+def _round_half_away(v: float) -> int:
+  return int(math.floor(abs(v) + 0.5)) * (1 if v >= 0 else -1)
+
+
+def quantize_multiplier(real: float) -> tuple:
+  """(M, shift) with real ~ M * 2^(shift - 31), host only: 0 -> (0, 0); otherwise real = frac * 2^exp (frexp,
+  0.5 <= frac < 1), M = round_half_away(frac * 2^31), M == 2^31 becomes (2^30, exp + 1); exp < -31 gives (0, 0), and
+  exp > 30 raises ValueError."""
+  real = float(real)
+  if not math.isfinite(real) or real < 0.0:
+    raise ValueError(f"the real multiplier must be finite and not negative (got {real})")
+  if real == 0.0:
+    return 0, 0
+  frac, exp = math.frexp(real)
+  m = _round_half_away(frac * float(1 << 31))      # (frac * 2^31 is exact in float64)
+  if m == 1 << 31:
+    m, exp = 1 << 30, exp + 1
+  if exp < -31:
+    return 0, 0
+  if exp > 30:
+    raise ValueError(f"the real multiplier {real} needs a left shift of {exp} > 30")
+  return m, exp
+
+
+def activation_range(fused: int, s_y: float, zp_y: int, bits: int) -> tuple:
+  """(act_min, act_max): the integer range of a fused activation on the output grid (s_y, zp_y) of `bits` (8 or 16).
+  NONE: the type's range; RELU: (max(qmin, zp_y), qmax); RELU6 / RELU_N1_TO_1: zp_y + round_half_away(f / s_y) of
+  their float bounds, clamped to the type. Any other code raises ValueError."""
+  if bits not in (8, 16):
+    raise ValueError(f"bits must be 8 or 16 (got {bits})")
+  qmin, qmax = -(1 << (bits - 1)), (1 << (bits - 1)) - 1
+  fused, zp_y = int(fused), int(zp_y)
+
+  def grid(f: float) -> int:
+    return min(max(zp_y + _round_half_away(f / float(s_y)), qmin), qmax)
+  if fused == FUSED_NONE:
+    return qmin, qmax
+  if fused == FUSED_RELU:
+    return max(qmin, zp_y), qmax
+  if fused == FUSED_RELU6:
+    return grid(0.0), grid(6.0)
+  if fused == FUSED_RELU_N1_TO_1:
+    return grid(-1.0), grid(1.0)
+  raise ValueError(f"fused activation {fused} is neither NONE, RELU, RELU_N1_TO_1 nor RELU6")
+
+
+class QfcMultipliers:
+  """Checked multiplier and shift tables on the device (qfc_multipliers): what qfc_output / qfc_output_i16 take in
+  place of host tables, so that repeated calls for one op upload them once."""
+
+  def __init__(self, multiplier: torch.Tensor, shift: torch.Tensor, rows: int, bits: int):
+    self.multiplier, self.shift, self.rows, self.bits = multiplier, shift, rows, bits
+
+
+def qfc_multipliers(multiplier, shift, rows: int, bits: int) -> QfcMultipliers:
+  """The host tables `multiplier` / `shift` (1 or rows entries each) of an op with `bits`-bit activations, checked
+  as qfc_output (8) / qfc_output_i16 (16) check them, on the device."""
+  if bits not in QFC_SHIFT_RANGE:
+    raise ValueError(f"bits must be 8 or 16 (got {bits})")
+  return _qfc_output_tables("qfc_multipliers", multiplier, shift, int(rows), bits)
+
+
+def _qfc_output_tables(who: str, multiplier, shift, rows: int, bits: int) -> QfcMultipliers:
+  """The host tables of multipliers and shifts, checked (M >= 0, shift within the entry's range), as device int32."""
+  if isinstance(multiplier, QfcMultipliers):
+    if shift is not None or multiplier.rows != rows or multiplier.bits != bits:
+      raise ValueError(f"{who}: the prepared multipliers are for {multiplier.rows} rows and {multiplier.bits}-bit"
+                       f" activations (and take no `shift` beside them), not for {rows} rows and {bits} bits")
+    return multiplier
+  m = np.asarray(multiplier, np.int64).reshape(-1)
+  s = np.asarray(shift, np.int64).reshape(-1)
+  if m.size != s.size or m.size not in (1, rows):
+    raise ValueError(f"{who}: multiplier and shift need 1 or rows = {rows} entries each (got {m.size} and {s.size})")
+  lo, hi = QFC_SHIFT_RANGE[bits]
+  if np.any(m < 0) or np.any(m > 0x7FFFFFFF):
+    raise ValueError(f"{who}: a multiplier is outside [0, 2^31 - 1]")
+  if np.any(s < lo) or np.any(s > hi):
+    raise ValueError(f"{who}: a shift is outside [{lo}, {hi}]")
+  return QfcMultipliers(rt.to_device(m.astype(np.int32)), rt.to_device(s.astype(np.int32)), rows, bits)
+
+
+def _qfc_output_common(who: str, xq, dtype, target: CompareTarget, rows: int, d: int, bias, bias_dtype):
+  if _qfc_block(who, xq, dtype, target, rows, d) != 0:
+    raise ValueError(f"{who}: a static op has one accumulator per output; blockwise scales are not available")
+  if bias is not None:
+    if not isinstance(bias, torch.Tensor):
+      bias = rt.to_device(np.ascontiguousarray(np.asarray(bias).reshape(-1)))
+    if bias.dtype != bias_dtype or not bias.is_cuda or bias.numel() != rows:
+      name = str(bias_dtype).replace("torch.", "")
+      raise TypeError(f"{who}: the bias must be {name} with {rows} entries, got {bias.dtype} with {bias.numel()}")
+    bias = bias.contiguous().view(-1)
+  return xq if xq.is_contiguous() else xq.contiguous(), bias
+
+
+def qfc_output(xq: torch.Tensor, x_zero_point: int, target: CompareTarget, rows: int, d: int, bias, multiplier, shift,
+               out_zero_point: int, act_min: int, act_max: int) -> torch.Tensor:
+  """What a static int8 FULLY_CONNECTED op stores: int8 [n, rows] =
+  clamp(mbqm32(sat32(Sum_k (xq - x_zero_point) q_w + bias), M, s) + out_zero_point, act_min, act_max) of int8
+  activations xq [n, d] and the stored integer weight of `target` (per tensor or per channel, as ops.qfc_forward
+  reads it); `bias` None or int32 [rows] (array or device tensor); `multiplier` / `shift` host tables of 1 or rows
+  entries (quantize_multiplier), M >= 0 and shift in [-31, 30], or qfc_multipliers' result with `shift` None.
+  include/mi355q.h, "Integer execution, through to the stored output". Does not synchronize."""
+  rt.require_gpu()
+  rows, d = int(rows), int(d)
+  xq, bias = _qfc_output_common("qfc_output", xq, torch.int8, target, rows, d, bias, torch.int32)
+  tables = _qfc_output_tables("qfc_output", multiplier, shift, rows, 8)
+  m_dev, s_dev = tables.multiplier, tables.shift
+  n = xq.shape[0]
+  q = rt.empty((n, rows), torch.int8)
+  L = _ffi.lib()
+  nbytes = L.mi355q_qfc_output_workspace_bytes(rows, d)
+  ws = rt.empty((max(nbytes, 1),), torch.uint8)
+  _ffi.check(L.mi355q_qfc_output_i8(rt.ptr(xq), n, d, int(x_zero_point), rt.ptr(target.data), COMPARE_KINDS[target.kind],
+                                    rows, rt.ptr(bias), rt.ptr(m_dev), rt.ptr(s_dev), m_dev.numel(), int(out_zero_point),
+                                    int(act_min), int(act_max), rt.ptr(q), rt.ptr(ws), nbytes, rt.stream_ptr()))
+  return q
+
+
+def qfc_output_i16(xq: torch.Tensor, target: CompareTarget, rows: int, d: int, bias, multiplier, shift, act_min: int,
+                   act_max: int) -> torch.Tensor:
+  """What a static int16-activation FULLY_CONNECTED op stores: int16 [n, rows] =
+  clamp((clamp(Sum_k xq q_w + bias, -2^47, 2^47 - 1) * Mr + 2^(T - 1)) >> T, act_min, act_max) with Mr the multiplier
+  rounded to 15 bits and T = 15 - shift; `bias` None or int64 [rows]; M >= 0 and shift in [-31, 14]; no zero points.
+  Does not synchronize."""
+  rt.require_gpu()
+  rows, d = int(rows), int(d)
+  xq, bias = _qfc_output_common("qfc_output_i16", xq, torch.int16, target, rows, d, bias, torch.int64)
+  tables = _qfc_output_tables("qfc_output_i16", multiplier, shift, rows, 16)
+  m_dev, s_dev = tables.multiplier, tables.shift
+  n = xq.shape[0]
+  q = rt.empty((n, rows), torch.int16)
+  L = _ffi.lib()
+  nbytes = L.mi355q_qfc_output_workspace_bytes(rows, d)
+  ws = rt.empty((max(nbytes, 1),), torch.uint8)
+  _ffi.check(L.mi355q_qfc_output_i16(rt.ptr(xq), n, d, rt.ptr(target.data), COMPARE_KINDS[target.kind], rows, rt.ptr(bias),
+                                     rt.ptr(m_dev), rt.ptr(s_dev), m_dev.numel(), int(act_min), int(act_max), rt.ptr(q),
+                                     rt.ptr(ws), nbytes, rt.stream_ptr()))
+  return q
 
 
 def sqdiff_cols(a: torch.Tensor, b: torch.Tensor, out: tuple | None = None):

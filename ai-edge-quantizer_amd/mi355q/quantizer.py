@@ -247,7 +247,8 @@ class Quantizer:
   def validate_layer_execution(self, calibration_data: Any, signature_key: Optional[str] = None,
                                save_folder: Optional[str] = None, model_name: Optional[str] = None,
                                follow_input_transforms: bool = False,
-                               int16_activations: bool = False) -> model_validator.LayerExecutionComparison:
+                               int16_activations: bool = False,
+                               quantized_outputs: bool = False) -> model_validator.LayerExecutionComparison:
     """Executes every quantized FULLY_CONNECTED op of the last quantize() result in integers on the calibration
     samples and compares it with the float product: error = (1/n) ||Yq - Y||^2 per op with its signal, MSE, SNR,
     per-channel errors, token count and mode (model_validator.compare_layer_execution). Unlike
@@ -259,14 +260,19 @@ class Quantizer:
     {signature key: such a list}. Ops behind an inserted Hadamard rotation or OSCAR multiply are listed in `.skipped`
     unless `follow_input_transforms` is set; then the samples go through the inserted op's own constant first. Ops
     that read an INT16 activation (static_wi8_ai16) are listed in `.skipped` unless `int16_activations` is set; then
-    they are executed with an exact int64 accumulator and every entry also carries `activation_bits`."""
+    they are executed with an exact int64 accumulator and every entry also carries `activation_bits`. With
+    `quantized_outputs` a static op is also executed through to the INT8 / INT16 tensor it stores (bias, fixed-point
+    multiplier, output zero point, fused activation) and compared with the float op's own act(X W^T + b): every entry
+    gains `output_bits`, and such an op `fused_activation` and the `final_*` figures, or `final_skipped` with the
+    reason."""
     quantized_model = self._result.quantized_model
     if quantized_model is None:
       raise ValueError("No quantized model available to validate.")
     samples = self._signature_samples(calibration_data, signature_key)
     results = model_validator.compare_layer_execution(self.float_model, bytes(quantized_model), samples, signature_key,
                                                       follow_input_transforms=follow_input_transforms,
-                                                      int16_activations=int16_activations)
+                                                      int16_activations=int16_activations,
+                                                      quantized_outputs=quantized_outputs)
     if save_folder:
       if model_name is None:
         model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"

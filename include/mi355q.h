@@ -1052,6 +1052,81 @@ int32_t mi355q_qfc_forward_i16(const int16_t* xq, int64_t n, int64_t d, const fl
                                int32_t block, float* y_out, int64_t* acc_out, void* workspace, size_t workspace_bytes,
                                void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Integer execution, through to the stored output (csrc/qfc_out.hip): what a
+ * static FULLY_CONNECTED op (static_wi8_ai8, static_wi8_ai16) leaves in its
+ * INT8 / INT16 output tensor, the tensor the next op reads: accumulator, bias,
+ * fixed-point multiplier, output zero point, the fused activation's integer
+ * range. The arithmetic is this library's own definition, modelled on LiteRT's
+ * integer FULLY_CONNECTED; agreement with LiteRT's kernels has not been checked,
+ * the claim is bit equality with the statement below. There is no blockwise
+ * form: a static op has one accumulator per output.
+ *
+ * xq, w, w_kind, rows and x_zero_point are as for mi355q_qfc_forward_i8 /
+ * mi355q_qfc_forward_i16 (weight zero points 0). bias is NULL (0) or has rows
+ * entries; multiplier and shift have mcount in {1, rows} entries (M, s below:
+ * one for the tensor, or one per output channel r).
+ *
+ * mi355q_qfc_output_i8 (xq int8 [n, d], bias int32, q_out int8 [n, rows]):
+ *   acc = Sum_k (xq[t,k] - x_zero_point) * w[r,k]      (int32, exact, formed as
+ *         the i8 forward entry forms it; no weight-sums launch when the zero
+ *         point is 0)
+ *   a   = sat32(int64(acc) + bias[r])
+ *   mbqm32(a, M, s):  L = max(s, 0), R = max(-s, 0)
+ *     v = sat32(int64(a) * 2^L)
+ *     p = int64(v) * M
+ *     h = (p + (p >= 0 ? 2^30 : 1 - 2^30)) / 2^31      (C++ truncating division)
+ *     mask = 2^R - 1
+ *     r = (h >> R) + ((h & mask) > (mask >> 1) + (h < 0))
+ *   q_out[t,r] = clamp(r + out_zero_point, act_min, act_max)
+ * sat32 clamps to [-2^31, 2^31 - 1]. The two sat32 are THIS LIBRARY'S CHOICE
+ * where LiteRT's int32 arithmetic would overflow (a + bias, a * 2^L): with them
+ * every intermediate is defined for every int32 input. Precondition: M >= 0 and
+ * s in [-31, 30] (what a quantized multiplier of a positive real below 2^30 is);
+ * the entry clamps s into that range so that no undefined shift is executed,
+ * and does not check M (|p| stays below 2^62 for every int32 M).
+ *
+ * mi355q_qfc_output_i16 (xq int16 [n, d], bias int64, q_out int16 [n, rows];
+ * no zero points):
+ *   acc = Sum_k xq[t,k] * w[r,k]                         (int64, exact: the two
+ *         int8 planes of the i16 forward entry plus 128 Sum_k w[r,k])
+ *   a   = clamp(acc + bias[r], -2^47, 2^47 - 1)
+ *   Mr  = M < 0x7FFF0000 ? (M + 2^15) >> 16 : 0x7FFF
+ *   T   = 15 - s
+ *   r   = (a * Mr + 2^(T - 1)) >> T                      (arithmetic shift)
+ *   q_out[t,r] = clamp(r, act_min, act_max)
+ * Precondition: M >= 0 and s in [-31, 14] (T in [1, 46]; |a * Mr| <= 2^62); the
+ * entry clamps s into that range, and a bias beyond +-2^62 acts as +-2^62 (the
+ * clamp of a gives the same).
+ *
+ * Routes are the forward entries': xq and w 16-byte aligned and d % 64 == 0
+ * take v_mfma_i32_16x16x64_i8 with the forward kernels' lane and tile maps (a
+ * wave owns 64 x 64 outputs, under int16 32 x 64 in two planes). The epilogue
+ * runs on the accumulator tile IN REGISTERS and only q_out is stored: no
+ * [n, rows] accumulator or float array is written to memory. In the C / D map a
+ * lane's values of a tile column all belong to channel l & 15, so bias,
+ * multiplier and shift are read once per 16-channel tile and lane. Every other
+ * d or alignment: one thread per output, the same bits.
+ *
+ * Refused before any launch, with the forward entries' texts where they overlap:
+ * negative shapes, null xq / w / multiplier / shift / q_out, another w_kind,
+ * mcount outside {1, rows}, x_zero_point / out_zero_point outside int8,
+ * act_min > act_max or either outside the output type (MI355Q_BAD_ARG);
+ * d > 65536 (MI355Q_UNSUPPORTED); a workspace that is NULL or smaller than
+ * mi355q_qfc_output_workspace_bytes(rows, d) = 4 * rows rounded up to 256 bytes
+ * where one is needed: under int8 when x_zero_point != 0, under int16 always
+ * (MI355Q_BAD_ARG). After those n == 0 or rows == 0 enqueues nothing.
+ * ------------------------------------------------------------------------ */
+size_t mi355q_qfc_output_workspace_bytes(int64_t rows, int64_t d);
+int32_t mi355q_qfc_output_i8(const int8_t* xq, int64_t n, int64_t d, int32_t x_zero_point, const void* w, int32_t w_kind,
+                             int64_t rows, const int32_t* bias, const int32_t* multiplier, const int32_t* shift,
+                             int64_t mcount, int32_t out_zero_point, int32_t act_min, int32_t act_max, int8_t* q_out,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int32_t mi355q_qfc_output_i16(const int16_t* xq, int64_t n, int64_t d, const void* w, int32_t w_kind, int64_t rows,
+                              const int64_t* bias, const int32_t* multiplier, const int32_t* shift, int64_t mcount,
+                              int32_t act_min, int32_t act_max, int16_t* q_out, void* workspace, size_t workspace_bytes,
+                              void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
