@@ -144,6 +144,8 @@ PROTOTYPES = {
                                      c_i32, c_i32, c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_qfc_output_i16": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr, c_i64, c_i32, c_i32,
                                       c_ptr, c_ptr, c_size, c_ptr]),
+    "mi355q_conv_patches_nhwc": (c_i32, [c_ptr, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                         c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
     "mi355q_sqdiff_cols_workspace_bytes": (c_size, [c_i64, c_i64]),
     "mi355q_sqdiff_cols_f64": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_size, c_ptr]),
     "mi355q_clock_probe": (c_i32, [c_f64, c_ptr, c_ptr]),

@@ -22,6 +22,7 @@ from . import schema
 from .transformations import graph_edits
 from .utils import flexbuffer
 from .utils import tfl_flatbuffer_utils
+from .utils import tflite_flatbuffer as tfl_flatbuffer
 from .utils import validation_utils
 
 DEFAULT_SIGNATURE_KEY = "serving_default"
@@ -846,12 +847,69 @@ def _fc_option(op, field: str) -> int:
   return int(getattr(op.builtinOptions, field, 0) or 0) if op.builtinOptions is not None else 0
 
 
-def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray):
-  """An OutputPlan, or the FINAL_SKIP_* reason there is none."""
+# `conv_2d`: CONV_2D ops beside the FULLY_CONNECTED ones
+_CONV_2D = 3
+_CONV_2D_OPTIONS_TYPE = 1      # Conv2DOptions in the BuiltinOptions union
+SKIP_CONV_FILTER = "the filter is not a constant 4-D float32 tensor"
+SKIP_CONV_GROUPS = "the filter's input channels differ from the sample's (grouped convolution)"
+SKIP_CONV_OPTIONS = "a stride or dilation below 1, or an unknown padding"
+SKIP_CONV_GEOMETRY = "no positive output size, or a reduction dimension above 65536"
+SKIP_CONV_BLOCKWISE = "the filter has blockwise scales"
+_CONV_OPTION_FIELDS = (("padding", "padding", "i8", 0), ("stride_w", "strideW", "i32", 0), ("stride_h", "strideH", "i32", 0),
+                       ("fused_activation_function", "fusedActivationFunction", "i8", 0),
+                       ("dilation_w_factor", "dilationWFactor", "i32", 1), ("dilation_h_factor", "dilationHFactor", "i32", 1))
+
+
+def conv_2d_options(op) -> Optional[dict]:
+  """Conv2DOptions of a CONV_2D op as {padding (0 SAME, 1 VALID), stride_w, stride_h, fused_activation_function,
+  dilation_w_factor, dilation_h_factor}, in the schema's field order (ids 0 to 5). The flatbuffer layer keeps the
+  table as an OpaqueTableT, whose scalars are read by field id with the schema's defaults for absent fields (0, and 1
+  for the dilations); a decoded object with the generated API's attribute names is read as well; an op without
+  options has every default. None when the op carries the options of another op type."""
+  o = op.builtinOptions
+  if o is None:
+    return {name: default for name, _, _, default in _CONV_OPTION_FIELDS}
+  if isinstance(o, tfl_flatbuffer.OpaqueTableT):
+    if int(getattr(op, "builtinOptionsType", 0) or 0) != _CONV_2D_OPTIONS_TYPE:
+      return None
+    return {name: int(o.scalar(i, code, default)) for i, (name, _, code, default) in enumerate(_CONV_OPTION_FIELDS)}
+  if not hasattr(o, "strideW"):
+    return None
+  out = {}
+  for name, attr, _, default in _CONV_OPTION_FIELDS:
+    v = getattr(o, attr, None)
+    out[name] = default if v is None else int(v)
+  return out
+
+
+def _conv_option(op, field: str) -> int:
+  """_fc_option for a CONV_2D: its fused activation; FC-only fields (weightsFormat) are default."""
+  if field != "fusedActivationFunction":
+    return 0
+  options = conv_2d_options(op)
+  return -1 if options is None else options["fused_activation_function"]
+
+
+def _conv_2d_ops(m, sg_index: int):
+  """(op, input 0 name, filter tensor, output name) of every CONV_2D op of a subgraph."""
+  sg = m.subgraphs[sg_index]
+  out = []
+  for op in sg.operators or []:
+    if int(m.operatorCodes[op.opcodeIndex].builtinCode) != _CONV_2D or len(op.inputs) < 2 or op.inputs[1] < 0:
+      continue
+    out.append((op, schema.tensor_name(sg.tensors[op.inputs[0]]), sg.tensors[op.inputs[1]],
+                schema.tensor_name(sg.tensors[op.outputs[0]])))
+  return out
+
+
+def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray,
+                 option=_fc_option):
+  """An OutputPlan, or the FINAL_SKIP_* reason there is none. `option(op, field)` reads an op's options
+  (_conv_option for a CONV_2D, whose FC-only fields are default)."""
   from . import ops
-  if _fc_option(fc, "weightsFormat") != 0 or _fc_option(ref_op, "weightsFormat") != 0:
+  if option(fc, "weightsFormat") != 0 or option(ref_op, "weightsFormat") != 0:
     return FINAL_SKIP_WEIGHTS_FORMAT
-  fused, float_fused = _fc_option(fc, "fusedActivationFunction"), _fc_option(ref_op, "fusedActivationFunction")
+  fused, float_fused = option(fc, "fusedActivationFunction"), option(ref_op, "fusedActivationFunction")
   if fused not in ops.FUSED_ACTIVATION_NAMES or float_fused not in ops.FUSED_ACTIVATION_NAMES:
     return FINAL_SKIP_ACTIVATION
   # ---- the output tensor
@@ -931,6 +989,29 @@ class LayerExecutionKernels:
 
   def rows(self, x, first: int, count: int):
     return x[first:first + count]
+
+  def sample4d(self, value):
+    """A rank-4 sample entry (array or device tensor) as a contiguous float32 [N, H, W, C] tensor (`conv_2d`)."""
+    import torch
+    from . import runtime as rt
+    return rt.on_device(rt.resident_sample(value), torch.float32).contiguous()
+
+  def patches(self, x, kernel: tuple, strides: tuple, dilations: tuple, padding: str, pad_value, first: int, count: int):
+    """Rows first .. first + count - 1 of the [N OH OW, KH KW C] patch rows of x [N, H, W, C], in x's own type
+    (float32, int8 or int16), padded taps holding `pad_value` (ops.conv_patches)."""
+    from . import ops
+    return ops.conv_patches(x, kernel[0], kernel[1], strides, dilations, padding, pad_value, first, count)
+
+  def quantize_dynamic_images(self, x, patch_rows: int):
+    """(q int8 [N, H, W, C], scale float32 [N patch_rows]): every image quantized as a whole, one scale per batch
+    element (ops.qfc_quantize_rows on [N, H W C]), and the scale of every patch row, `patch_rows` per image in
+    order: patch row t reads image t // patch_rows. The index is formed on the device."""
+    import torch
+    from . import ops
+    n = int(x.shape[0])
+    q, scale = ops.qfc_quantize_rows(x.view(n, -1))
+    image = torch.arange(n * patch_rows, device=x.device) // patch_rows
+    return q.view(x.shape), scale[image]
 
   def transform(self, x, kind: str, multiplier, hadamard_size: int):
     """The inserted op's own map on rows of length d: x * multiplier, or x R with R = blockdiag(H_h / sqrt(h))."""
@@ -1033,6 +1114,8 @@ class LayerExecutionComparison(LayerOutputComparison):
   with `quantized_outputs` also `output_bits` and, for a static op executed through to its stored output,
   `fused_activation`, `final_signal`, `final_error`, `final_output_mse`, `final_output_snr` and
   `final_per_channel_error`, or `final_skipped` with the reason there are none;
+  with `conv_2d` also `op` ("FULLY_CONNECTED" or "CONV_2D"), and for a CONV_2D (rows = O, d = KH KW I, tokens = patch
+  rows) `kernel`, `strides`, `dilations`, `padding` and `output_hw`;
   `skipped[name]` is the reason an op was not computed."""
 
   def as_dict(self) -> dict:
@@ -1056,7 +1139,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                             kernels: Optional[LayerExecutionKernels] = None,
                             follow_input_transforms: bool = False,
                             int16_activations: bool = False,
-                            quantized_outputs: bool = False) -> LayerExecutionComparison:
+                            quantized_outputs: bool = False,
+                            conv_2d: bool = False) -> LayerExecutionComparison:
   """Executes every quantized FULLY_CONNECTED op in integers on the calibration samples and compares it with the
   float model's product, for every op of the float model with a constant 2-D float32 weight [rows, d] whose input 0
   is in `samples` (the {tensor name: array or device tensor} maps calibrate() takes; tensors of any rank are rows of
@@ -1104,6 +1188,27 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
   fused activation NONE, RELU, RELU_N1_TO_1 or RELU6; weightsFormat DEFAULT; multipliers within the op's shift range.
   Otherwise the pre-bias figures stay and the entry carries `final_skipped` (a FINAL_SKIP_* reason) and no final_*
   figure. Without the keyword nothing changes.
+
+  With `conv_2d` every CONV_2D op of the float model is executed as well, whose filter is a constant float32
+  [O, KH, KW, I] and whose input 0 has samples of rank 4, [N, H, W, I]. A TFLite filter's reduction dimension
+  K = KH KW I is contiguous per output channel, so the filter is the [rows = O, d = K] weight above (per tensor or per
+  channel along dimension 0; kinds i8 / i4 / i2) and the op is the same product on the [N OH OW, K] patch rows of the
+  sample (ops.conv_patches, the geometry of ops.conv_geometry from the op's Conv2DOptions: conv_2d_options), gathered
+  in chunks of at most 4096 rows, so that no [all patches, K] array exists. Y = patches(X, pad 0.0) W^T. The mode is
+  read as for FULLY_CONNECTED. "static": the whole sample is quantized once with the tensor's (s_x, zp_x), 8 or 16
+  bits, and the patches are gathered from the INTEGER tensor with pad element zp_x; since q(0.0) = zp_x these are the
+  bits of quantizing float patches padded with 0.0, with one read of the sample instead of KH KW. "dynamic": one
+  scale per batch element, every image quantized as a whole (ops.qfc_quantize_rows on [N, H W I]), int8 patches with
+  pad 0, and patch row t takes the scale of image t // (OH OW). "weight_only": patches(X) dequant(W^)^T. With
+  `quantized_outputs` the epilogue above runs on the patch rows, the fused activation read from Conv2DOptions; the
+  output tensor [N, OH, OW, O] is the [n, O] rows as they stand. `follow_input_transforms` does not apply: a conv
+  behind an inserted op is "the quantized op reads a transformed input". This is this library's definition, modelled
+  on LiteRT's CONV_2D; agreement with LiteRT's kernels has not been checked. EVERY entry then carries `op`
+  ("FULLY_CONNECTED" or "CONV_2D"), and a conv entry `rows` = O, `d` = K, `tokens` = the number of patch rows, and
+  `kernel` [KH, KW], `strides` and `dilations` [h, w], `padding` ("SAME" / "VALID") and `output_hw` (of the first
+  sample). Further skip reasons: SKIP_CONV_FILTER, SKIP_CONV_GROUPS (I differs from the sample's channels),
+  SKIP_CONV_OPTIONS, SKIP_CONV_GEOMETRY, SKIP_CONV_BLOCKWISE, and SKIP_SAMPLE_SHAPE for a sample that is not rank 4.
+  Without the keyword nothing changes.
   """
   kernels = kernels or LayerExecutionKernels()
   samples = list(samples)
@@ -1263,6 +1368,194 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
       entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
       if isinstance(final, OutputPlan):
         from . import ops
+        f_diff, f_ref = kernels.host(final_sums)
+        f_channel = np.asarray(f_diff, np.float64) / tokens
+        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
+        f_mse = f_error / rows
+        entry.update(fused_activation=ops.FUSED_ACTIVATION_NAMES[final.fused], final_signal=f_signal,
+                     final_error=f_error, final_output_mse=f_mse, final_output_snr=(f_signal / rows) / (f_mse + 1e-9),
+                     final_per_channel_error=f_channel)
+      elif final is not None:
+        entry["final_skipped"] = final
+    if conv_2d:
+      out.results[y_name]["op"] = "FULLY_CONNECTED"
+  if not conv_2d:
+    return out
+
+  # ---- CONV_2D: the same product on patch rows (the docstring's last section)
+  from . import ops
+  for ref_op, x_name, w, y_name in _conv_2d_ops(ref, sg_ref):
+    w_name = schema.tensor_name(w)
+    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
+        or min(int(v) for v in w.shape) < 1):
+      out.skipped[y_name] = SKIP_CONV_FILTER
+      continue
+    rows, kh, kw, channels = (int(v) for v in w.shape)
+    d = kh * kw * channels
+    conv = producer_op.get(y_name)
+    if conv is None or code(conv) != _CONV_2D or len(conv.inputs) < 2 or conv.inputs[0] < 0 or conv.inputs[1] < 0:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    options, float_options = conv_2d_options(conv), conv_2d_options(ref_op)
+    geometry = ("padding", "stride_h", "stride_w", "dilation_h_factor", "dilation_w_factor")
+    if (options is None or float_options is None or any(options[k] != float_options[k] for k in geometry)
+        or options["padding"] not in ops.CONV_PADDING_NAMES or min(options[k] for k in geometry[1:]) < 1):
+      out.skipped[y_name] = SKIP_CONV_OPTIONS
+      continue
+    strides, dilations = (options["stride_h"], options["stride_w"]), (options["dilation_h_factor"], options["dilation_w_factor"])
+    padding = ops.CONV_PADDING_NAMES[options["padding"]]
+    # ---- the filter the target op reads: the integer constant itself, or a DEQUANTIZE of it
+    read = tgt_sg.tensors[conv.inputs[1]]
+    target, through_dequantize = read, False
+    if not _has_data(tgt.buffers, read):
+      deq = producers.get(int(conv.inputs[1]))
+      if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
+        out.skipped[y_name] = SKIP_TARGET
+        continue
+      target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
+    if schema.tensor_name(target) != w_name or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if target.type in (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16):
+      out.skipped[y_name] = SKIP_FLOAT_TARGET
+      continue
+    # ---- the activation it reads (follow_input_transforms does not apply: a conv behind an inserted op is skipped)
+    x_in = tgt_sg.tensors[conv.inputs[0]]
+    if x_in.type == schema.TensorType.INT16 and not int16_activations:
+      out.skipped[y_name] = SKIP_INT16
+      continue
+    x_quant, activation_bits = None, None
+    if x_in.type in (schema.TensorType.INT8, schema.TensorType.INT16):
+      q = x_in.quantization
+      source = name(conv.inputs[0])
+      quantize = producers.get(int(conv.inputs[0]))
+      if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
+        source = name(quantize.inputs[0])
+      if q is None or q.scale is None or len(q.scale) != 1 or source != x_name or through_dequantize:
+        out.skipped[y_name] = SKIP_INPUT
+        continue
+      zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
+      activation_bits = 16 if x_in.type == schema.TensorType.INT16 else 8
+      if (activation_bits == 16 and zero_point != 0) or not -128 <= zero_point <= 127:
+        out.skipped[y_name] = SKIP_INPUT
+        continue
+      x_quant = (float(np.float32(q.scale[0])), zero_point)
+      mode = MODE_STATIC
+    elif x_in.type == schema.TensorType.FLOAT32 and name(conv.inputs[0]) == x_name:
+      mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
+    else:
+      out.skipped[y_name] = SKIP_INPUT
+      continue
+    # ---- the filter as a [O, K] constant: K = KH KW I is contiguous per output channel
+    values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
+    plan = _target_plan(w_name, values, tgt, target)
+    if plan is None or not plan.dequantized:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if plan.kind not in ("i8", "i4", "i2"):
+      out.skipped[y_name] = SKIP_KIND
+      continue
+    if plan.scale is None:
+      out.skipped[y_name] = SKIP_CONV_BLOCKWISE
+      continue
+    if not (plan.channels == 1 or (plan.channels == rows and plan.inner == d)):
+      out.skipped[y_name] = SKIP_TARGET      # (per-channel scales along another dimension than 0)
+      continue
+    if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
+      out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
+      continue
+    present = [s[x_name] for s in samples if x_name in s]
+    if not present:
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    if any(len(v.shape) != 4 for v in present):
+      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
+      continue
+    if any(int(v.shape[3]) != channels for v in present):
+      out.skipped[y_name] = SKIP_CONV_GROUPS
+      continue
+    try:
+      if d > ops.QFC_MAX_D:
+        raise ValueError("K")
+      shapes = [ops.conv_geometry(int(v.shape[1]), int(v.shape[2]), kh, kw, strides, dilations, padding) for v in present
+                if int(v.shape[0]) > 0]
+    except ValueError:
+      out.skipped[y_name] = SKIP_CONV_GEOMETRY
+      continue
+    if not shapes:            # (every sample of the input was empty)
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    w_dev = kernels.weight(values, rows, d)
+    t_dev = kernels.target(plan)
+    dq_dev = kernels.dequantized(t_dev, rows, d) if mode == MODE_WEIGHT_ONLY else None
+    final, final_sums, bias_dev, float_bias_dev = None, None, None, None
+    if quantized_outputs and mode == MODE_STATIC:
+      final = _output_plan(ref, ref.subgraphs[sg_ref], ref_op, tgt, tgt_sg, conv, rows, activation_bits, x_quant[0],
+                           plan.scale, option=_conv_option)
+    if isinstance(final, OutputPlan):
+      bias_dev = None if final.bias is None else kernels.bias(final.bias)
+      float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
+    sums, tokens = None, 0
+    gather = (kh, kw), strides, dilations, padding
+    for value in present:
+      if int(value.shape[0]) == 0:
+        continue
+      x = kernels.sample4d(value)
+      oh, ow, _, _ = ops.conv_geometry(int(x.shape[1]), int(x.shape[2]), kh, kw, strides, dilations, padding)
+      n = int(x.shape[0]) * oh * ow
+      # the whole sample is quantized ONCE and the patches are gathered from the integer tensor, padded with the zero
+      # point: q(0.0) = zp_x, so these are the bits of quantizing float patches padded with 0.0
+      if mode == MODE_DYNAMIC:
+        xq_all, scale_rows = kernels.quantize_dynamic_images(x, oh * ow)
+        pad = 0
+      elif mode == MODE_STATIC and activation_bits == 16:
+        xq_all, x_scale = kernels.quantize_static16(x, x_quant[0])
+        pad = 0
+      elif mode == MODE_STATIC:
+        xq_all, x_scale = kernels.quantize_static(x, *x_quant)
+        pad = x_quant[1]
+      for first in range(0, n, EXECUTION_CHUNK_ROWS):
+        count = min(EXECUTION_CHUNK_ROWS, n - first)
+        xc = kernels.patches(x, *gather, 0.0, first, count)
+        y = kernels.gemm(xc, w_dev)
+        if mode == MODE_WEIGHT_ONLY:
+          yq = kernels.gemm(xc, dq_dev)
+        else:
+          xq = kernels.patches(xq_all, *gather, pad, first, count)
+          if mode == MODE_DYNAMIC:
+            yq = kernels.forward(xq, kernels.rows(scale_rows, first, count), 0, t_dev, rows, d)
+          elif activation_bits == 16:
+            yq = kernels.forward16(xq, x_scale, t_dev, rows, d)
+          else:
+            yq = kernels.forward(xq, x_scale, x_quant[1], t_dev, rows, d)
+        sums = kernels.sqdiff(yq, y, sums)
+        if isinstance(final, OutputPlan):
+          if activation_bits == 16:
+            q_out = kernels.output16(xq, t_dev, rows, d, bias_dev, final.multiplier, final.shift, final.act_min,
+                                     final.act_max)
+          else:
+            q_out = kernels.output(xq, x_quant[1], t_dev, rows, d, bias_dev, final.multiplier, final.shift,
+                                   final.zero_point, final.act_min, final.act_max)
+          final_sums = kernels.sqdiff(kernels.dequantize_output(q_out, final.scale, final.zero_point),
+                                      kernels.reference_output(y, float_bias_dev, final.float_fused), final_sums)
+      tokens += n
+    sq_diff, sq_ref = kernels.host(sums)
+    per_channel = np.asarray(sq_diff, np.float64) / tokens
+    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
+    mse = error / rows
+    entry = out.results[y_name] = {
+        "op": "CONV_2D", "weight": w_name, "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
+        "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations), "padding": padding,
+        "output_hw": [shapes[0][0], shapes[0][1]],
+        "signal": signal, "error": error, "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
+        "per_channel_error": per_channel}
+    if follow_input_transforms:
+      entry.update(input_transform=TRANSFORM_NONE, hadamard_size=0)
+    if int16_activations:
+      entry["activation_bits"] = activation_bits
+    if quantized_outputs:
+      entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
+      if isinstance(final, OutputPlan):
         f_diff, f_ref = kernels.host(final_sums)
         f_channel = np.asarray(f_diff, np.float64) / tokens
         f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)

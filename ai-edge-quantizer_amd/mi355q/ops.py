@@ -8,6 +8,7 @@ include/mi355q.h.
 from __future__ import annotations
 
 import contextlib as _contextlib
+import ctypes
 import math
 import os
 import threading
@@ -1282,6 +1283,98 @@ def qfc_output_i16(xq: torch.Tensor, target: CompareTarget, rows: int, d: int, b
                                      rt.ptr(m_dev), rt.ptr(s_dev), m_dev.numel(), int(act_min), int(act_max), rt.ptr(q),
                                      rt.ptr(ws), nbytes, rt.stream_ptr()))
   return q
+
+
+# (include/mi355q.h, "Patch gather for CONV_2D")
+CONV_PADDING_NAMES = {0: "SAME", 1: "VALID"}
+_CONV_DTYPES = {torch.int8: np.int8, torch.int16: np.int16, torch.float32: np.float32}
+
+
+def _pair(value, what: str) -> tuple:
+  """An int, or (h, w), as two Python integers."""
+  if isinstance(value, (tuple, list)):
+    if len(value) != 2:
+      raise ValueError(f"{what} must be an integer or an (h, w) pair (got {value!r})")
+    return int(value[0]), int(value[1])
+  return int(value), int(value)
+
+
+def _padding_name(padding) -> str:
+  name = CONV_PADDING_NAMES.get(padding, padding) if not isinstance(padding, str) else padding.upper()
+  if name not in ("SAME", "VALID"):
+    raise ValueError(f"padding must be 'SAME' (0) or 'VALID' (1), got {padding!r}")
+  return name
+
+
+def conv_geometry(h: int, w: int, kh: int, kw: int, stride, dilation, padding) -> tuple:
+  """(oh, ow, pad_top, pad_left) of a CONV_2D over an h x w image, host arithmetic on Python integers by TFLite's
+  rule: eff = (k - 1) dil + 1; SAME: out = ceil(in / stride); VALID: out = (in + stride - eff) // stride;
+  total = max(0, (out - 1) stride + eff - in) and pad_before = total // 2 (an odd total puts the extra row after).
+  `stride` and `dilation` are integers or (h, w) pairs, `padding` "SAME" / "VALID" (or the schema's 0 / 1). Raises
+  ValueError when an output dimension is not positive."""
+  (sh, sw), (dh, dw) = _pair(stride, "stride"), _pair(dilation, "dilation")
+  name = _padding_name(padding)
+  h, w, kh, kw = int(h), int(w), int(kh), int(kw)
+  if min(h, w, kh, kw, sh, sw, dh, dw) < 1:
+    raise ValueError(f"image {h} x {w}, kernel {kh} x {kw}, strides {sh}, {sw} and dilations {dh}, {dw} must be positive")
+
+  def axis(size: int, k: int, stride_: int, dil: int) -> tuple:
+    eff = (k - 1) * dil + 1
+    out = -(-size // stride_) if name == "SAME" else (size + stride_ - eff) // stride_
+    if out < 1:
+      raise ValueError(f"no positive output size: {size} inputs, kernel {k}, stride {stride_}, dilation {dil}, {name}")
+    return out, max(0, (out - 1) * stride_ + eff - size) // 2
+  (oh, top), (ow, left) = axis(h, kh, sh, dh), axis(w, kw, sw, dw)
+  return oh, ow, top, left
+
+
+def conv_patches(x: torch.Tensor, kh: int, kw: int, stride, dilation, padding, pad_value=0, first: int = 0,
+                 count: int | None = None) -> torch.Tensor:
+  """The patch rows of an NHWC activation: x [N, H, W, C] (int8, int16 or float32, on the device) ->
+  [count, kh kw C] of the same dtype, rows first .. first + count - 1 of the N OH OW patch rows (default: all from
+  `first` on), row t = (n, oh, ow) in that order and column (i kw + j) C + c the tap (i, j), channel c; a tap outside
+  the image holds `pad_value` (the activation's zero point for an integer tensor). The geometry is conv_geometry's.
+  A byte copy: a NaN pad keeps its payload. The rows are what qfc_forward / qfc_forward_i16 / qfc_output read
+  against a filter [O, kh, kw, C] viewed as [O, kh kw C]. Does not synchronize."""
+  rt.require_gpu()
+  if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in _CONV_DTYPES:
+    raise TypeError(f"expected an int8, int16 or float32 device tensor, got {getattr(x, 'dtype', type(x))}"
+                    f" on {getattr(x, 'device', 'the host')}")
+  if x.dim() != 4:
+    raise ValueError(f"expected an [N, H, W, C] tensor, got {tuple(x.shape)}")
+  n_img, h, w, c = (int(v) for v in x.shape)
+  kh, kw = int(kh), int(kw)
+  (sh, sw), (dh, dw) = _pair(stride, "stride"), _pair(dilation, "dilation")
+  if min(n_img, h, w, c) < 1:
+    raise ValueError(f"every dimension of x must be positive, got {tuple(x.shape)}")
+  oh, ow, top, left = conv_geometry(h, w, kh, kw, (sh, sw), (dh, dw), padding)
+  k = kh * kw * c
+  if k > QFC_MAX_D:
+    raise ValueError(f"K = {kh} x {kw} x {c} = {k} exceeds {QFC_MAX_D}, the forward entries' limit")
+  rows_all = n_img * oh * ow
+  if rows_all > 0x7FFFFFFF:
+    raise ValueError(f"{rows_all} patch rows exceed INT32_MAX")
+  first = int(first)
+  count = rows_all - first if count is None else int(count)
+  if first < 0 or count < 0 or first + count > rows_all:
+    raise ValueError(f"rows [{first}, {first} + {count}) are outside the {rows_all} patch rows")
+  np_dtype = _CONV_DTYPES[x.dtype]
+  pad = np.asarray(pad_value)
+  if pad.size != 1:
+    raise ValueError("pad_value must be one element")
+  if pad.dtype != np_dtype:
+    if np_dtype != np.float32:
+      if pad.dtype.kind not in "iub" or not np.iinfo(np_dtype).min <= int(pad.reshape(())) <= np.iinfo(np_dtype).max:
+        raise ValueError(f"pad_value {pad_value!r} is no {np.dtype(np_dtype).name}")
+    pad = pad.astype(np_dtype)
+  pad_bytes = ctypes.create_string_buffer(pad.tobytes(), pad.itemsize)
+  if not x.is_contiguous():
+    x = x.contiguous()
+  out = rt.empty((count, k), x.dtype)
+  _ffi.check(_ffi.lib().mi355q_conv_patches_nhwc(rt.ptr(x), x.element_size(), n_img, h, w, c, kh, kw, sh, sw, dh, dw, top,
+                                                 left, oh, ow, first, count, ctypes.cast(pad_bytes, ctypes.c_void_p),
+                                                 rt.ptr(out), rt.stream_ptr()))
+  return out
 
 
 def sqdiff_cols(a: torch.Tensor, b: torch.Tensor, out: tuple | None = None):

@@ -1127,6 +1127,51 @@ int32_t mi355q_qfc_output_i16(const int16_t* xq, int64_t n, int64_t d, const voi
                               int32_t act_min, int32_t act_max, int16_t* q_out, void* workspace, size_t workspace_bytes,
                               void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Patch gather for CONV_2D (csrc/conv_patches.hip): an NHWC activation
+ * x [N, H, W, C] becomes the rows the integer FULLY_CONNECTED entries above
+ * read. A TFLite filter is [O, KH, KW, I]: its reduction dimension
+ * K = KH KW C is contiguous per output channel, so after this gather a
+ * CONV_2D is the product xq [n, K] w [O, K]^T those entries execute.
+ *
+ * Statement. For t in [first_row, first_row + row_count):
+ *   n = t / (OH OW)      oh = (t / OW) % OH      ow = t % OW
+ * and for k = (kh KW + kw) C + c:
+ *   ih = oh stride_h - pad_top + kh dil_h
+ *   iw = ow stride_w - pad_left + kw dil_w
+ *   out[(t - first_row) K + k] = x[((n H + ih) W + iw) C + c]
+ *                                          when 0 <= ih < H and 0 <= iw < W
+ *                              = *pad_element                    otherwise
+ * Elements are elem_bytes (1, 2 or 4) wide and are copied as bytes: a float
+ * NaN keeps its payload and -0.0 its sign. pad_element is a HOST pointer to one
+ * element, read before the call returns (the activation's zero point for an
+ * integer tensor, so that q - zp = 0 in a padded tap). OH, OW, pad_top and
+ * pad_left are the caller's (for TFLite's SAME / VALID: ops.conv_geometry);
+ * whatever they are, no element outside x is read. All index arithmetic is
+ * 64-bit: N H W C may exceed 2^31. The window [first_row, first_row +
+ * row_count) lets a caller walk the patch rows in chunks, so that no
+ * [N OH OW, K] array has to exist.
+ *
+ * Routes. C elem_bytes % 16 == 0 with x and out 16-byte aligned: every 16-byte
+ * piece of a patch row lies inside one tap and rows of out are 16-byte
+ * aligned; one lane moves one piece (a 16-byte load, or the splatted pad
+ * element, and a 16-byte store) and consecutive lanes write consecutive pieces.
+ * Everything else: one element per thread. Both write the same bytes.
+ *
+ * Refused before any launch: elem_bytes outside {1, 2, 4}; N, H, W, C, KH, KW,
+ * OH, OW, a stride or a dilation that is not positive; a negative first_row or
+ * row_count; first_row + row_count > N OH OW (MI355Q_BAD_ARG); K > 65536, the
+ * forward entries' limit; N OH OW > INT32_MAX; an activation beyond 2^62 bytes
+ * (MI355Q_UNSUPPORTED). After those row_count == 0 enqueues nothing, whatever
+ * the pointers; otherwise a null x, out or pad_element is MI355Q_BAD_ARG. A
+ * request of 2^32 units or more (a launch holds fewer work-items) runs as one
+ * launch whose lanes stride over the units with a 64-bit index.
+ * ------------------------------------------------------------------------ */
+int32_t mi355q_conv_patches_nhwc(const void* x, int32_t elem_bytes, int64_t N, int64_t H, int64_t W, int64_t C, int32_t KH,
+                                 int32_t KW, int32_t stride_h, int32_t stride_w, int32_t dil_h, int32_t dil_w,
+                                 int32_t pad_top, int32_t pad_left, int64_t OH, int64_t OW, int64_t first_row,
+                                 int64_t row_count, const void* pad_element, void* out, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
