@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256) void xtx_bf16x3_kernel(XtxArgs a) {
 // patch is 8 x 4 of these tiles = its 32 CUs, resident together. Tile (ti, tj) covers rows 128 ti.. and columns
 // 256 tj..; it is needed when 2 tj <= ti (the tile on the diagonal of an even tile row also computes 128 columns
 // above the diagonal: valid entries of the symmetric product, never read). Same products, same accumulator
-// structure, same k order per output as the narrow kernel: the same bits (tests/test_gpu_gptq.py).
+// structure, same k order per output as the narrow kernel: the same bits (tests/test_gpu_xtx_routes.py).
 constexpr int kWideA = 3 * kPlaneTileB;            // 12 KB: three planes of 128 rows, one k tile
 constexpr int kWideB = 6 * kPlaneTileB;            // 24 KB: three planes of 256 rows
 constexpr int kWideKt = kWideA + kWideB;           // 36 KB per k tile
@@ -347,7 +347,7 @@ __global__ __launch_bounds__(512) void xtx_bf16x3_wide_kernel(XtxArgs a) {
 // The wide kernel with FOUR one-k-tile buffers instead of two two-k-tile stages (the same 144 KB of LDS): see the staging
 // comment inside. SQ counters of the kernel above (profiles/r05_xtx_bound.txt): its waves spend 32 % of their cycles in
 // s_waitcnt / s_barrier -- all eight at the same time -- and the MFMA pipe is 57 % busy. Same products, same accumulator
-// structure, same k order per output: the same bits (tests/test_gpu_gptq.py).
+// structure, same k order per output: the same bits (tests/test_gpu_xtx_routes.py).
 template <int ALT>
 __global__ __launch_bounds__(512) void xtx_bf16x3_deep_kernel(XtxArgs a) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char lds[];
