@@ -5,27 +5,26 @@
 //                           keeps the row in registers between the maximum and the rounding (one read of x), 16 floats
 //                           per lane and chunk, and stores 16 int8 at once; the scalar route reads the row twice.
 //   weight_sums_kernel      wsum[r][b] = Sum_k q_w[r][b * L + k] (int32, exact), the zero-point term of the accumulator
-//                           (qfc_frag.h, with the weight fragments: qfc16.hip uses both as well).
-//   qfc_mfma_kernel         acc = Xq W^^T on the int8 matrix cores. Both operands are contiguous along the reduction
-//                           dimension, so a lane's A fragment is 16 consecutive bytes of a row of Xq and its B fragment
-//                           16 consecutive elements of a row of W^ (8 bytes of int4, 4 bytes of int2, unpacked and
-//                           sign-extended in registers). A wave owns 64 tokens x 64 output channels = 4 x 4 MFMA tiles:
-//                           4 + 4 fragments feed 16 v_mfma_i32_16x16x64_i8, the next step's fragments are in flight
-//                           while they run, and the four waves of a workgroup (128 x 128) share rows through L1 / L2.
-//                           Block 32 uses v_mfma_i32_16x16x32_i8 (8 bytes per lane). Blockwise scales flush the int32
-//                           tile into float32 sums after every block, in ascending order, without FMA.
+//                           (qfc_frag.h, with the weight fragments: qfc16.hip and qfc_out.hip use both as well).
+//   qfc_mfma_kernel         acc = Xq W^^T on the int8 matrix cores: the main loop of qfc_tile.h with int8 activations.
+//                           A lane's A fragment is 16 consecutive bytes of a row of Xq and its B fragment 16
+//                           consecutive elements of a row of W^ (8 bytes of int4, 4 bytes of int2, unpacked and
+//                           sign-extended in registers). A wave owns 64 tokens x 64 output channels = 4 x 4 MFMA tiles
+//                           of v_mfma_i32_16x16x64_i8, and the four waves of a workgroup (128 x 128) share rows
+//                           through L1 / L2. Block 32 uses v_mfma_i32_16x16x32_i8 (8 bytes per lane). This file adds
+//                           the float rescale: blockwise scales flush the int32 tile into float32 sums after every
+//                           block, in ascending order, without FMA.
 //   qfc_generic_kernel      one thread per output, element by element: every other shape and alignment, same bits.
 //   sqdiff_cols_*_kernel    per column Sum_t (a - b)^2 and Sum_t b^2 in float64 in a fixed order.
 #include "common.h"
 #include "compare_target.h"
-#include "qfc_frag.h"
+#include "qfc_tile.h"
 
 namespace mi355q {
 namespace {
 
 constexpr int kThreads = kQfcThreads;
-constexpr int kMaxD = 65536;           // d * 255 * 128 < 2^31
-constexpr int kVecMaxD = 16384;        // a row of the vector quantizer: 256 threads x 4 chunks x 16 floats
+constexpr int kVecMaxD = 16384;       // a row of the vector quantizer: 256 threads x 4 chunks x 16 floats
 
 struct __attribute__((aligned(16))) F4 { float x, y, z, w; };
 struct __attribute__((aligned(16))) U4 { uint32_t x, y, z, w; };
@@ -139,115 +138,44 @@ struct FwdArgs {
   int kind;
 };
 
-template <int KSTEP> struct XFrag;
-template <> struct XFrag<64> {
-  static __device__ __forceinline__ I32x4 load(const int8_t* p) { return *reinterpret_cast<const I32x4*>(p); }
-  static __device__ __forceinline__ I32x4 zero() { return I32x4{0, 0, 0, 0}; }
-  static __device__ __forceinline__ I32x4 mfma(I32x4 a, I32x4 b, I32x4 c) {
-    return __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct XFrag<32> {
-  static __device__ __forceinline__ long load(const int8_t* p) { return *reinterpret_cast<const long*>(p); }
-  static __device__ __forceinline__ long zero() { return 0; }
-  static __device__ __forceinline__ I32x4 mfma(long a, long b, I32x4 c) {
-    return __builtin_amdgcn_mfma_i32_16x16x32_i8(a, b, c, 0, 0, 0);
-  }
+struct ChanF {
+  float sw;      // the channel's weight scale
+  int corr;      // zp * Sum_k q_w[r][k]
 };
 
-constexpr int MF = 16;             // MFMA tile edge
-constexpr int TM = 4;              // MFMA tiles per wave along tokens and along output channels
-constexpr int WT = TM * MF;        // a wave's tile edge (64)
-constexpr int BT = 2 * WT;         // a workgroup's tile edge (2 x 2 waves)
-
-// MFMA route: d % KSTEP == 0, xq and w 16-byte aligned (so every fragment load is aligned to its own size).
-// grid: x = output-channel tiles, y = token tiles.
 template <int KIND, int KSTEP, bool BLOCKWISE>
 __global__ __launch_bounds__(kThreads) void qfc_mfma_kernel(FwdArgs g) {
-  using XF = XFrag<KSTEP>;
-  using RW = RawW<KIND, KSTEP>;
-  using Frag = typename FragOf<KSTEP>::T;
-  constexpr int E = KSTEP / 4;     // consecutive elements per lane and step
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const long long t0 = static_cast<long long>(blockIdx.y) * BT + (wave >> 1) * WT;
-  const long long r0 = static_cast<long long>(blockIdx.x) * BT + (wave & 1) * WT;
-  if (t0 >= g.n || r0 >= g.rows) return;     // (the whole wave; the kernel has no barrier)
-  const int fr = lane & 15, fg = lane >> 4;
+  constexpr int TA = QfcTile<int8_t>::TA;
+  QfcWave wv;
+  if (!qfc_wave<int8_t>(wv, g.n, g.rows)) return;
 
-  const int8_t* xp[TM];
-  long long we[TM];
-  bool xok[TM], wok[TM];
+  I32x4 acc[QfcTile<int8_t>::TM][TB];
+  float yf[TA][TB][4];
 #pragma unroll
-  for (int a = 0; a < TM; ++a) {
-    const long long t = t0 + a * MF + fr, r = r0 + a * MF + fr;
-    xok[a] = t < g.n;
-    wok[a] = r < g.rows;
-    xp[a] = g.xq + (xok[a] ? t : 0) * g.d + fg * E;
-    we[a] = (wok[a] ? r : 0) * g.d + fg * E;
-  }
-
-  I32x4 acc[TM][TM];
-  float yf[TM][TM][4];
+  for (int a = 0; a < TA; ++a)
 #pragma unroll
-  for (int a = 0; a < TM; ++a)
-#pragma unroll
-    for (int b = 0; b < TM; ++b) {
-      acc[a][b] = I32x4{0, 0, 0, 0};
+    for (int b = 0; b < TB; ++b)
 #pragma unroll
       for (int i = 0; i < 4; ++i) yf[a][b][i] = 0.0f;
-    }
-  float sx[TM][4];
-  if (BLOCKWISE) {
+  float sx[TA][4];
+  if constexpr (BLOCKWISE) {
 #pragma unroll
-    for (int a = 0; a < TM; ++a)
+    for (int a = 0; a < TA; ++a)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const long long t = t0 + a * MF + fg * 4 + i;
+        const long long t = wv.t0 + a * MF + wv.fg * 4 + i;
         sx[a][i] = t < g.n ? g.x_scale[g.x_per_row ? t : 0] : 0.0f;
       }
-  }
-
-  const int steps = static_cast<int>(g.d / KSTEP);
-  const int steps_per_block = BLOCKWISE ? g.block / KSTEP : steps;
-  Frag xc[TM], xn[TM];
-  typename RW::T wc[TM], wn[TM];
+    // p_b = fl(float(acc_b) * fl(s_x * s_w[r, b])), y = y + p_b: blocks in ascending order, no FMA
+    qfc_main_loop<int8_t, KIND, KSTEP>(wv, g.xq, g.w, g.n, g.rows, g.d, acc, g.block / KSTEP, [=, &acc, &yf](int bi) {
 #pragma unroll
-  for (int a = 0; a < TM; ++a) {
-    xc[a] = xok[a] ? XF::load(xp[a]) : XF::zero();
-    wc[a] = wok[a] ? RW::load(g.w, we[a]) : RW::zero();
-  }
-  int in_block = 0, bi = 0;
-  for (int s = 0; s < steps; ++s) {
-    if (s + 1 < steps) {     // the next step's fragments fly while this step's MFMAs run
-      const long long k = static_cast<long long>(s + 1) * KSTEP;
-#pragma unroll
-      for (int a = 0; a < TM; ++a) {
-        xn[a] = xok[a] ? XF::load(xp[a] + k) : XF::zero();
-        wn[a] = wok[a] ? RW::load(g.w, we[a] + k) : RW::zero();
-      }
-    }
-    Frag wf[TM];
-#pragma unroll
-    for (int b = 0; b < TM; ++b) wf[b] = RW::unpack(wc[b]);
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TM; ++b) acc[a][b] = XF::mfma(xc[a], wf[b], acc[a][b]);
-#pragma unroll
-    for (int a = 0; a < TM; ++a) {
-      xc[a] = xn[a];
-      wc[a] = wn[a];
-    }
-    if (BLOCKWISE && ++in_block == steps_per_block) {
-      // p_b = fl(float(acc_b) * fl(s_x * s_w[r, b])), y = y + p_b: blocks in ascending order, no FMA
-#pragma unroll
-      for (int b = 0; b < TM; ++b) {
-        const long long r = r0 + b * MF + fr;
+      for (int b = 0; b < TB; ++b) {
+        const long long r = wv.r0 + b * MF + wv.fr;
         const bool rok = r < g.rows;
         const float sw = rok ? g.w_scale[r * g.nblocks + bi] : 0.0f;
         const int corr = (rok && g.zp != 0) ? g.zp * g.wsum[r * g.nblocks + bi] : 0;
 #pragma unroll
-        for (int a = 0; a < TM; ++a)
+        for (int a = 0; a < TA; ++a)
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const float sc = sx[a][i] * sw;
@@ -256,38 +184,27 @@ __global__ __launch_bounds__(kThreads) void qfc_mfma_kernel(FwdArgs g) {
             acc[a][b][i] = 0;
           }
       }
-      in_block = 0;
-      ++bi;
-    }
+    });
+  } else {
+    qfc_main_loop<int8_t, KIND, KSTEP>(wv, g.xq, g.w, g.n, g.rows, g.d, acc);
   }
 
-  // C / D map of the 16x16 MFMAs: column (output channel) = lane & 15, row (token) = 4 (lane >> 4) + register
-#pragma unroll
-  for (int b = 0; b < TM; ++b) {
-    const long long r = r0 + b * MF + fr;
-    if (r >= g.rows) continue;
-    float sw = 0.0f;
-    int corr = 0;
-    if (!BLOCKWISE) {
-      sw = g.w_scale[g.w_mode == 1 ? r : 0];
-      corr = g.zp != 0 ? g.zp * g.wsum[r] : 0;
-    }
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const long long t = t0 + a * MF + fg * 4 + i;
-        if (t >= g.n) continue;
+  qfc_walk_outputs<int8_t>(
+      wv, g.n, g.rows,
+      [=](long long r) {
+        if (BLOCKWISE) return ChanF{0.0f, 0};
+        return ChanF{g.w_scale[g.w_mode == 1 ? r : 0], g.zp != 0 ? g.zp * g.wsum[r] : 0};
+      },
+      [=, &acc, &yf](const ChanF& c, int a, int b, int i, long long t, long long r) {
         if (BLOCKWISE) {
           g.y[t * g.rows + r] = yf[a][b][i];
         } else {
-          const int v = acc[a][b][i] - corr;
-          const float sc = g.x_scale[g.x_per_row ? t : 0] * sw;
+          const int v = acc[a][b][i] - c.corr;
+          const float sc = g.x_scale[g.x_per_row ? t : 0] * c.sw;
           g.y[t * g.rows + r] = static_cast<float>(v) * sc;
           if (g.acc) g.acc[t * g.rows + r] = v;
         }
-      }
-  }
+      });
 }
 
 // Generic route: one thread per output element, one weight element at a time.
@@ -295,14 +212,10 @@ __global__ __launch_bounds__(kThreads) void qfc_generic_kernel(FwdArgs g) {
   const long long total = g.n * g.rows, step = static_cast<long long>(gridDim.x) * kThreads;
   for (long long o = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; o < total; o += step) {
     const long long t = o / g.rows, r = o % g.rows;
-    const int8_t* xr = g.xq + t * g.d;
     const float s_x = g.x_scale[g.x_per_row ? t : 0];
     float y = 0.0f;
     for (int b = 0; b < g.nblocks; ++b) {
-      int acc = 0;
-      const long long k0 = static_cast<long long>(b) * g.block;
-      for (long long k = k0; k < k0 + g.block; ++k)
-        acc += static_cast<int>(xr[k]) * weight_element(g.w, g.kind, r * g.d + k);
+      int acc = qfc_dot<int>(g.xq + t * g.d, g.w, g.kind, r * g.d, static_cast<long long>(b) * g.block, g.block, 0);
       if (g.zp != 0) acc -= g.zp * g.wsum[r * g.nblocks + b];
       if (g.w_mode == 2) {
         const float sc = s_x * g.w_scale[r * g.nblocks + b];
@@ -316,11 +229,6 @@ __global__ __launch_bounds__(kThreads) void qfc_generic_kernel(FwdArgs g) {
     }
     g.y[o] = y;
   }
-}
-
-size_t fwd_workspace(int64_t rows, int64_t d, int32_t block) {
-  const size_t nblocks = block > 0 ? static_cast<size_t>(d / block) : 1;
-  return (static_cast<size_t>(rows) * nblocks * sizeof(int32_t) + 255) & ~static_cast<size_t>(255);
 }
 
 template <int KIND>
@@ -407,7 +315,7 @@ extern "C" int32_t mi355q_qfc_quantize_rows_f32(const float* x, int64_t n, int64
 
 extern "C" size_t mi355q_qfc_forward_workspace_bytes(int64_t rows, int64_t d, int32_t block) {
   if (rows <= 0 || d <= 0 || block < 0 || (block > 0 && d % block)) return 0;
-  return fwd_workspace(rows, d, block);
+  return wsum_workspace(rows, block > 0 ? d / block : 1);
 }
 
 extern "C" int32_t mi355q_qfc_forward_i8(const int8_t* xq, int64_t n, int64_t d, const float* x_scale,
@@ -418,61 +326,44 @@ extern "C" int32_t mi355q_qfc_forward_i8(const int8_t* xq, int64_t n, int64_t d,
   clear_error();
   if (n < 0 || d < 0 || rows < 0) return fail(MI355Q_BAD_ARG, "negative shape");
   if (!xq || !x_scale || !w || !w_scale || !y_out) return fail(MI355Q_BAD_ARG, "null pointer");
-  if (w_kind != MI355Q_CMP_I8 && w_kind != MI355Q_CMP_I4 && w_kind != MI355Q_CMP_I2)
-    return fail(MI355Q_BAD_ARG, "weight kind %d is not I8, I4 or I2", w_kind);
+  if (const int32_t bad = check_weight_kind(w_kind)) return bad;
   if (x_zero_point < -128 || x_zero_point > 127)
     return fail(MI355Q_BAD_ARG, "activation zero point %d is outside int8", x_zero_point);
-  if (block != 0 && block != 32 && block != 64 && block != 128 && block != 256)
-    return fail(MI355Q_BAD_ARG, "block must be 0, 32, 64, 128 or 256 (got %d)", block);
-  if (block > 0 && d % block)
-    return fail(MI355Q_BAD_SHAPE, "Quantized dimension %lld is not divisible by block size %d.",
-                static_cast<long long>(d), block);
-  if (x_scale_count != 1 && x_scale_count != n)
-    return fail(MI355Q_BAD_ARG, "x_scale_count must be 1 or n = %lld (got %lld)", static_cast<long long>(n),
-                static_cast<long long>(x_scale_count));
-  const int64_t nblocks = block > 0 ? d / block : 1;
-  const bool blockwise = block > 0 && w_scale_count == rows * nblocks;   // (block = 0 with per-tensor / per-channel scales)
-  if (!blockwise && w_scale_count != 1 && w_scale_count != rows)
-    return fail(MI355Q_BAD_ARG, "w_scale_count must be 1, rows = %lld or rows * d / block (got %lld)",
-                static_cast<long long>(rows), static_cast<long long>(w_scale_count));
-  if (blockwise && acc_out) return fail(MI355Q_BAD_ARG, "acc_out is not available with blockwise scales");
-  if (d > kMaxD) return fail(MI355Q_UNSUPPORTED, "d = %lld exceeds %d (the int32 accumulator)", static_cast<long long>(d), kMaxD);
+  if (const int32_t bad = check_block(block, d)) return bad;
+  bool blockwise;
+  if (const int32_t bad = check_scale_counts(n, rows, d, block, x_scale_count, w_scale_count, acc_out != nullptr, &blockwise))
+    return bad;
+  if (d > kQfcMaxD)
+    return fail(MI355Q_UNSUPPORTED, "d = %lld exceeds %d (the int32 accumulator)", static_cast<long long>(d), kQfcMaxD);
   if (n == 0 || rows == 0) return MI355Q_OK;
   if (d == 0) return fail(MI355Q_BAD_ARG, "d must be >= 1");
-  const size_t need = fwd_workspace(rows, d, blockwise ? block : 0);
+  const int64_t nblocks = blockwise ? d / block : 1;
+  const size_t need = wsum_workspace(rows, nblocks);
   if (x_zero_point != 0 && (!workspace || workspace_bytes < need))
     return fail(MI355Q_BAD_ARG, "workspace of %zu bytes is smaller than the %zu needed", workspace_bytes, need);
-  const int64_t row_tiles = (rows + BT - 1) / BT, tok_tiles = (n + BT - 1) / BT;
-  if (row_tiles > 0x7FFFFFFFLL || tok_tiles > 65535) return fail(MI355Q_UNSUPPORTED, "too many tiles for one launch");
+  dim3 grid;
+  if (const int32_t bad = tile_grid<int8_t>(n, rows, &grid)) return bad;
 
   FwdArgs g{};
   g.xq = xq; g.w = static_cast<const uint8_t*>(w); g.x_scale = x_scale; g.w_scale = w_scale;
   g.wsum = static_cast<const int32_t*>(workspace); g.y = y_out; g.acc = acc_out;
   g.n = n; g.rows = rows; g.d = d; g.x_per_row = x_scale_count != 1 ? 1 : 0;
   g.w_mode = blockwise ? 2 : (w_scale_count == rows && rows != 1) ? 1 : 0;
-  g.nblocks = blockwise ? static_cast<int>(nblocks) : 1;
+  g.nblocks = static_cast<int>(nblocks);
   g.block = blockwise ? block : static_cast<int>(d);
   g.zp = x_zero_point; g.kind = w_kind;
   hipStream_t st = as_stream(stream);
 
-  if (x_zero_point != 0) {
+  if (x_zero_point != 0) {      // (on both routes: the generic kernel subtracts zp * wsum as well)
     const int32_t st_sums = launch_weight_sums(g.w, w_kind, rows * g.nblocks, static_cast<long long>(g.block),
                                                static_cast<int32_t*>(workspace), st);
     if (st_sums != MI355Q_OK) return st_sums;
   }
 
-  const int kstep = blockwise && block == 32 ? 32 : 64;
-  const bool mfma = d % kstep == 0 && reinterpret_cast<uintptr_t>(xq) % 16 == 0 && reinterpret_cast<uintptr_t>(w) % 16 == 0;
-  if (mfma) {
-    const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(tok_tiles));
-    if (w_kind == MI355Q_CMP_I8) launch_mfma<MI355Q_CMP_I8>(g, blockwise, grid, st);
-    else if (w_kind == MI355Q_CMP_I4) launch_mfma<MI355Q_CMP_I4>(g, blockwise, grid, st);
-    else launch_mfma<MI355Q_CMP_I2>(g, blockwise, grid, st);
-  } else {
-    const long long total = n * rows, blocks = (total + kThreads - 1) / kThreads;
-    hipLaunchKernelGGL(qfc_generic_kernel, dim3(static_cast<unsigned>(blocks < (1 << 20) ? blocks : (1 << 20))),
-                       dim3(kThreads), 0, st, g);
-  }
+  if (mfma_route(xq, w, d, blockwise && block == 32 ? 32 : 64))
+    dispatch_kind(w_kind, [&](auto kind) { launch_mfma<decltype(kind)::value>(g, blockwise, grid, st); });
+  else
+    hipLaunchKernelGGL(qfc_generic_kernel, dim3(generic_blocks(n * rows)), dim3(kThreads), 0, st, g);
   MI355Q_CHECK_LAUNCH("integer fully-connected launch");
   return MI355Q_OK;
 }

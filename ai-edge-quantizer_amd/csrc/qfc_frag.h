@@ -1,5 +1,5 @@
-// What the integer FULLY_CONNECTED kernels of qfc.hip (int8 activations) and qfc16.hip (int16 activations) share:
-// the stored weight's elements, the per-row / per-block weight sums, and the B fragments of the int8 MFMAs.
+// The stored weight of the integer FULLY_CONNECTED kernels: its elements, the per-row / per-block weight sums, and the
+// B fragments of the int8 MFMAs. Included by qfc_tile.h (the main loop that qfc.hip, qfc16.hip and qfc_out.hip share).
 #pragma once
 
 #include "common.h"

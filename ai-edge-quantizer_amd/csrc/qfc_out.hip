@@ -3,23 +3,23 @@
 // activation's integer range, int8 / int16 store. No [n, rows] accumulator or float array exists: the MFMA kernels
 // run the epilogue on the accumulator tile in registers and store q_out alone.
 //
-//   qfc_out_mfma_kernel       the main loop of qfc.hip's qfc_mfma_kernel (K = 64, one accumulator per output): a wave
-//                             owns 64 tokens x 64 channels = 4 x 4 tiles of v_mfma_i32_16x16x64_i8. In the C / D map a
+//   qfc_out_mfma_kernel       the main loop of qfc_tile.h with int8 activations (K = 64, one accumulator per output): a
+//                             wave owns 64 tokens x 64 channels = 4 x 4 tiles of v_mfma_i32_16x16x64_i8. In the C / D map a
 //                             lane's 4 x 4 x 4 values all belong to the channels r0 + 16 b + (lane & 15), b = 0 .. 3: bias,
 //                             multiplier and shift are read once per b and serve 16 outputs each.
-//   qfc_out16_mfma_kernel     the main loop of qfc16.hip's qfc16_mfma_kernel (two int8 planes of the int16 activation,
-//                             32 tokens x 64 channels per wave), combined with 128 Sum w in int64 in the epilogue.
+//   qfc_out16_mfma_kernel     the same loop for int16 activations (two int8 planes, 32 tokens x 64 channels per
+//                             wave), written out here as in qfc16.hip; combined with 128 Sum w in int64 in the epilogue.
 //   qfc_out_generic_kernel,
 //   qfc_out16_generic_kernel  one thread per output, element by element: every other shape and alignment, same bits.
+// This file holds the two fixed-point epilogues; qfc.hip and qfc16.hip hold the float ones.
 #include "common.h"
 #include "compare_target.h"
-#include "qfc_frag.h"
+#include "qfc_tile.h"
 
 namespace mi355q {
 namespace {
 
 constexpr int kThreads = kQfcThreads;
-constexpr int kMaxD = 65536;           // d * 255 * 128 < 2^31 (i8); each int32 plane d * 128 * 128 <= 2^30 (i16)
 
 struct OutArgs {
   const void* xq;          // int8 / int16 [n, d]
@@ -94,91 +94,24 @@ __device__ __forceinline__ int16_t output16(long long acc, const Chan16& c, cons
   return static_cast<int16_t>(r < g.act_min ? g.act_min : r > g.act_max ? g.act_max : r);
 }
 
-constexpr int MF = 16;             // MFMA tile edge
-
 // ---------------------------------------------------------------- int8 activations
-constexpr int TM = 4;              // MFMA tiles per wave along tokens and along output channels
-constexpr int WT = TM * MF;        // a wave's tile edge (64)
-constexpr int BT = 2 * WT;         // a workgroup's tile edge (2 x 2 waves)
-
-// MFMA route: d % 64 == 0, xq and w 16-byte aligned. grid: x = output-channel tiles, y = token tiles.
 template <int KIND>
 __global__ __launch_bounds__(kThreads) void qfc_out_mfma_kernel(OutArgs g) {
-  using RW = RawW<KIND, 64>;
-  constexpr int KSTEP = 64, E = KSTEP / 4;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const long long t0 = static_cast<long long>(blockIdx.y) * BT + (wave >> 1) * WT;
-  const long long r0 = static_cast<long long>(blockIdx.x) * BT + (wave & 1) * WT;
-  if (t0 >= g.n || r0 >= g.rows) return;     // (the whole wave; the kernel has no barrier)
-  const int fr = lane & 15, fg = lane >> 4;
-  const int8_t* xq = static_cast<const int8_t*>(g.xq);
+  QfcWave wv;
+  if (!qfc_wave<int8_t>(wv, g.n, g.rows)) return;
+  I32x4 acc[QfcTile<int8_t>::TM][TB];
+  qfc_main_loop<int8_t, KIND, 64>(wv, static_cast<const int8_t*>(g.xq), g.w, g.n, g.rows, g.d, acc);
 
-  const int8_t* xp[TM];
-  long long we[TM];
-  bool xok[TM], wok[TM];
-#pragma unroll
-  for (int a = 0; a < TM; ++a) {
-    const long long t = t0 + a * MF + fr, r = r0 + a * MF + fr;
-    xok[a] = t < g.n;
-    wok[a] = r < g.rows;
-    xp[a] = xq + (xok[a] ? t : 0) * g.d + fg * E;
-    we[a] = (wok[a] ? r : 0) * g.d + fg * E;
-  }
-
-  I32x4 acc[TM][TM];
-#pragma unroll
-  for (int a = 0; a < TM; ++a)
-#pragma unroll
-    for (int b = 0; b < TM; ++b) acc[a][b] = I32x4{0, 0, 0, 0};
-
-  const int steps = static_cast<int>(g.d / KSTEP);
-  I32x4 xc[TM], xn[TM];
-  typename RW::T wc[TM], wn[TM];
-#pragma unroll
-  for (int a = 0; a < TM; ++a) {
-    xc[a] = xok[a] ? *reinterpret_cast<const I32x4*>(xp[a]) : I32x4{0, 0, 0, 0};
-    wc[a] = wok[a] ? RW::load(g.w, we[a]) : RW::zero();
-  }
-  for (int s = 0; s < steps; ++s) {
-    if (s + 1 < steps) {     // the next step's fragments fly while this step's MFMAs run
-      const long long k = static_cast<long long>(s + 1) * KSTEP;
-#pragma unroll
-      for (int a = 0; a < TM; ++a) {
-        xn[a] = xok[a] ? *reinterpret_cast<const I32x4*>(xp[a] + k) : I32x4{0, 0, 0, 0};
-        wn[a] = wok[a] ? RW::load(g.w, we[a] + k) : RW::zero();
-      }
-    }
-    I32x4 wf[TM];
-#pragma unroll
-    for (int b = 0; b < TM; ++b) wf[b] = RW::unpack(wc[b]);
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int b = 0; b < TM; ++b) acc[a][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xc[a], wf[b], acc[a][b], 0, 0, 0);
-#pragma unroll
-    for (int a = 0; a < TM; ++a) {
-      xc[a] = xn[a];
-      wc[a] = wn[a];
-    }
-  }
-
-  // C / D map of the 16x16 MFMAs: column (output channel) = lane & 15, row (token) = 4 (lane >> 4) + register
+  struct Chan {
+    Chan8 c;
+    int corr;      // zp_x * Sum_k q_w[r][k]
+  };
   int8_t* q = static_cast<int8_t*>(g.q);
-#pragma unroll
-  for (int b = 0; b < TM; ++b) {
-    const long long r = r0 + b * MF + fr;
-    if (r >= g.rows) continue;
-    const Chan8 c = chan8(g, r);
-    const int corr = g.zp_x != 0 ? g.zp_x * g.wsum[r] : 0;
-#pragma unroll
-    for (int a = 0; a < TM; ++a)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const long long t = t0 + a * MF + fg * 4 + i;
-        if (t >= g.n) continue;
-        q[t * g.rows + r] = output8(acc[a][b][i] - corr, c, g);
-      }
-  }
+  qfc_walk_outputs<int8_t>(
+      wv, g.n, g.rows, [=](long long r) { return Chan{chan8(g, r), g.zp_x != 0 ? g.zp_x * g.wsum[r] : 0}; },
+      [=, &acc](const Chan& c, int a, int b, int i, long long t, long long r) {
+        q[t * g.rows + r] = output8(acc[a][b][i] - c.corr, c.c, g);
+      });
 }
 
 // Generic route: one thread per output element, one weight element at a time.
@@ -188,51 +121,22 @@ __global__ __launch_bounds__(kThreads) void qfc_out_generic_kernel(OutArgs g) {
   int8_t* q = static_cast<int8_t*>(g.q);
   for (long long o = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; o < total; o += step) {
     const long long t = o / g.rows, r = o % g.rows;
-    const int8_t* xr = xq + t * g.d;
-    int acc = 0;
-    for (long long k = 0; k < g.d; ++k) acc += (static_cast<int>(xr[k]) - g.zp_x) * weight_element(g.w, g.kind, r * g.d + k);
-    q[o] = output8(acc, chan8(g, r), g);
+    q[o] = output8(qfc_dot<int>(xq + t * g.d, g.w, g.kind, r * g.d, 0, g.d, g.zp_x), chan8(g, r), g);
   }
 }
 
 // ---------------------------------------------------------------- int16 activations
-// Words x0 = (v0, v1), x1 = (v2, v3) of four consecutive int16 -> the word of their four high bytes, and the word of
-// their four low bytes with the top bit flipped (l_u - 128 as int8): qfc16.hip's split, one v_perm_b32 each.
-__device__ __forceinline__ int high_bytes(int x0, int x1) {
-  return static_cast<int>(__builtin_amdgcn_perm(static_cast<uint32_t>(x1), static_cast<uint32_t>(x0), 0x07050301u));
-}
-__device__ __forceinline__ int low_bytes_biased(int x0, int x1) {
-  return static_cast<int>(__builtin_amdgcn_perm(static_cast<uint32_t>(x1), static_cast<uint32_t>(x0), 0x06040200u) ^
-                          0x80808080u);
-}
-
-struct X16 { I32x4 a, b; };        // k = 0 .. 7 and 8 .. 15 of a lane's 16 consecutive int16
-
-__device__ __forceinline__ X16 load_x16(const int16_t* p) {
-  const I32x4* v = reinterpret_cast<const I32x4*>(p);
-  return X16{v[0], v[1]};
-}
-
-__device__ __forceinline__ void split_x16(const X16& r, I32x4& hi, I32x4& lo) {
-  hi = I32x4{high_bytes(r.a[0], r.a[1]), high_bytes(r.a[2], r.a[3]), high_bytes(r.b[0], r.b[1]), high_bytes(r.b[2], r.b[3])};
-  lo = I32x4{low_bytes_biased(r.a[0], r.a[1]), low_bytes_biased(r.a[2], r.a[3]), low_bytes_biased(r.b[0], r.b[1]),
-             low_bytes_biased(r.b[2], r.b[3])};
-}
-
-constexpr int TA = 2;              // MFMA tiles per wave along tokens (each in two planes)
-constexpr int TB = 4;              // MFMA tiles per wave along output channels
-constexpr int WTA = TA * MF;       // a wave's tokens (32)
-constexpr int WTB = TB * MF;       // a wave's output channels (64)
-constexpr int BTA = 2 * WTA;       // a workgroup's tokens (2 x 2 waves)
-constexpr int BTB = 2 * WTB;       // a workgroup's output channels
-
+// (the main loop written out, as in qfc16.hip's qfc16_mfma_kernel, which says why)
 template <int KIND>
 __global__ __launch_bounds__(kThreads) void qfc_out16_mfma_kernel(OutArgs g) {
   using RW = RawW<KIND, 64>;
+  using XF = Act<int16_t, 64>;
+  using T = QfcTile<int16_t>;
+  constexpr int TA = T::TA;
   constexpr int KSTEP = 64, E = KSTEP / 4;
   const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  const long long t0 = static_cast<long long>(blockIdx.y) * BTA + (wave >> 1) * WTA;
-  const long long r0 = static_cast<long long>(blockIdx.x) * BTB + (wave & 1) * WTB;
+  const long long t0 = static_cast<long long>(blockIdx.y) * T::BTA + (wave >> 1) * T::WTA;
+  const long long r0 = static_cast<long long>(blockIdx.x) * T::BTB + (wave & 1) * T::WTB;
   if (t0 >= g.n || r0 >= g.rows) return;     // (the whole wave; the kernel has no barrier)
   const int fr = lane & 15, fg = lane >> 4;
   const int16_t* xq = static_cast<const int16_t*>(g.xq);
@@ -262,33 +166,32 @@ __global__ __launch_bounds__(kThreads) void qfc_out16_mfma_kernel(OutArgs g) {
       al[a][b] = I32x4{0, 0, 0, 0};
     }
 
-  const X16 zero{I32x4{0, 0, 0, 0}, I32x4{0, 0, 0, 0}};
   const int steps = static_cast<int>(g.d / KSTEP);
-  X16 xc[TA], xn[TA];
+  typename XF::Raw xc[TA], xn[TA];
   typename RW::T wc[TB], wn[TB];
 #pragma unroll
-  for (int a = 0; a < TA; ++a) xc[a] = xok[a] ? load_x16(xp[a]) : zero;
+  for (int a = 0; a < TA; ++a) xc[a] = xok[a] ? XF::load(xp[a]) : XF::zero();
 #pragma unroll
   for (int b = 0; b < TB; ++b) wc[b] = wok[b] ? RW::load(g.w, we[b]) : RW::zero();
   for (int s = 0; s < steps; ++s) {
     if (s + 1 < steps) {     // the next step's fragments fly while this step's MFMAs run
       const long long k = static_cast<long long>(s + 1) * KSTEP;
 #pragma unroll
-      for (int a = 0; a < TA; ++a) xn[a] = xok[a] ? load_x16(xp[a] + k) : zero;
+      for (int a = 0; a < TA; ++a) xn[a] = xok[a] ? XF::load(xp[a] + k) : XF::zero();
 #pragma unroll
       for (int b = 0; b < TB; ++b) wn[b] = wok[b] ? RW::load(g.w, we[b] + k) : RW::zero();
     }
-    I32x4 wf[TB], xh[TA], xl[TA];
+    I32x4 wf[TB], xs[TA][2];      // xs[a]: the high and the biased low plane
 #pragma unroll
     for (int b = 0; b < TB; ++b) wf[b] = RW::unpack(wc[b]);      // once, for both planes
 #pragma unroll
-    for (int a = 0; a < TA; ++a) split_x16(xc[a], xh[a], xl[a]);
+    for (int a = 0; a < TA; ++a) XF::frags(xc[a], xs[a]);
 #pragma unroll
     for (int a = 0; a < TA; ++a)
 #pragma unroll
       for (int b = 0; b < TB; ++b) {
-        ah[a][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xh[a], wf[b], ah[a][b], 0, 0, 0);
-        al[a][b] = __builtin_amdgcn_mfma_i32_16x16x64_i8(xl[a], wf[b], al[a][b], 0, 0, 0);
+        ah[a][b] = mfma_i8<KSTEP>(xs[a][0], wf[b], ah[a][b]);
+        al[a][b] = mfma_i8<KSTEP>(xs[a][1], wf[b], al[a][b]);
       }
 #pragma unroll
     for (int a = 0; a < TA; ++a) xc[a] = xn[a];
@@ -322,34 +225,20 @@ __global__ __launch_bounds__(kThreads) void qfc_out16_generic_kernel(OutArgs g) 
   int16_t* q = static_cast<int16_t*>(g.q);
   for (long long o = static_cast<long long>(blockIdx.x) * kThreads + threadIdx.x; o < total; o += step) {
     const long long t = o / g.rows, r = o % g.rows;
-    const int16_t* xr = xq + t * g.d;
-    long long acc = 0;
-    for (long long k = 0; k < g.d; ++k)
-      acc += static_cast<long long>(static_cast<int>(xr[k]) * weight_element(g.w, g.kind, r * g.d + k));
-    q[o] = output16(acc, chan16(g, r), g);
+    q[o] = output16(qfc_dot<long long>(xq + t * g.d, g.w, g.kind, r * g.d, 0, g.d, 0), chan16(g, r), g);
   }
 }
 
-size_t out_workspace(int64_t rows) {
-  return (static_cast<size_t>(rows) * sizeof(int32_t) + 255) & ~static_cast<size_t>(255);
-}
-
-// What both entries refuse, in one order; 1 = carry on, otherwise the status to return.
+// What both entries refuse first, in one order.
 int32_t check_common(const void* xq, int64_t n, int64_t d, const void* w, int32_t w_kind, int64_t rows,
                      const int32_t* multiplier, const int32_t* shift, int64_t mcount, const void* q_out) {
   if (n < 0 || d < 0 || rows < 0) return fail(MI355Q_BAD_ARG, "negative shape");
   if (!xq || !w || !multiplier || !shift || !q_out) return fail(MI355Q_BAD_ARG, "null pointer");
-  if (w_kind != MI355Q_CMP_I8 && w_kind != MI355Q_CMP_I4 && w_kind != MI355Q_CMP_I2)
-    return fail(MI355Q_BAD_ARG, "weight kind %d is not I8, I4 or I2", w_kind);
+  if (const int32_t bad = check_weight_kind(w_kind)) return bad;
   if (mcount != 1 && mcount != rows)
     return fail(MI355Q_BAD_ARG, "mcount must be 1 or rows = %lld (got %lld)", static_cast<long long>(rows),
                 static_cast<long long>(mcount));
-  return 1;
-}
-
-unsigned generic_blocks(long long total) {
-  const long long blocks = (total + kThreads - 1) / kThreads;
-  return static_cast<unsigned>(blocks < (1 << 20) ? blocks : (1 << 20));
+  return MI355Q_OK;
 }
 
 }  // namespace
@@ -359,7 +248,7 @@ using namespace mi355q;
 
 extern "C" size_t mi355q_qfc_output_workspace_bytes(int64_t rows, int64_t d) {
   if (rows <= 0 || d <= 0) return 0;
-  return out_workspace(rows);
+  return wsum_workspace(rows, 1);
 }
 
 extern "C" int32_t mi355q_qfc_output_i8(const int8_t* xq, int64_t n, int64_t d, int32_t x_zero_point, const void* w,
@@ -368,22 +257,21 @@ extern "C" int32_t mi355q_qfc_output_i8(const int8_t* xq, int64_t n, int64_t d, 
                                         int32_t act_max, int8_t* q_out, void* workspace, size_t workspace_bytes,
                                         void* stream) {
   clear_error();
-  const int32_t common = check_common(xq, n, d, w, w_kind, rows, multiplier, shift, mcount, q_out);
-  if (common != 1) return common;
+  if (const int32_t bad = check_common(xq, n, d, w, w_kind, rows, multiplier, shift, mcount, q_out)) return bad;
   if (x_zero_point < -128 || x_zero_point > 127)
     return fail(MI355Q_BAD_ARG, "activation zero point %d is outside int8", x_zero_point);
   if (out_zero_point < -128 || out_zero_point > 127)
     return fail(MI355Q_BAD_ARG, "output zero point %d is outside int8", out_zero_point);
   if (act_min > act_max || act_min < -128 || act_max > 127)
     return fail(MI355Q_BAD_ARG, "activation range [%d, %d] is no range within int8", act_min, act_max);
-  if (d > kMaxD) return fail(MI355Q_UNSUPPORTED, "d = %lld exceeds %d (the int32 accumulator)", static_cast<long long>(d), kMaxD);
-  const size_t need = (rows > 0 && d > 0 && x_zero_point != 0) ? out_workspace(rows) : 0;
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return fail(MI355Q_BAD_ARG, "workspace of %zu bytes is smaller than the %zu needed", workspace ? workspace_bytes : size_t{0}, need);
+  if (d > kQfcMaxD)
+    return fail(MI355Q_UNSUPPORTED, "d = %lld exceeds %d (the int32 accumulator)", static_cast<long long>(d), kQfcMaxD);
+  const size_t need = (rows > 0 && d > 0 && x_zero_point != 0) ? wsum_workspace(rows, 1) : 0;
+  if (const int32_t bad = check_workspace(workspace, workspace_bytes, need)) return bad;
   if (n == 0 || rows == 0) return MI355Q_OK;
   if (d == 0) return fail(MI355Q_BAD_ARG, "d must be >= 1");
-  const int64_t row_tiles = (rows + BT - 1) / BT, tok_tiles = (n + BT - 1) / BT;
-  if (row_tiles > 0x7FFFFFFFLL || tok_tiles > 65535) return fail(MI355Q_UNSUPPORTED, "too many tiles for one launch");
+  dim3 grid;
+  if (const int32_t bad = tile_grid<int8_t>(n, rows, &grid)) return bad;
 
   OutArgs g{};
   g.xq = xq; g.w = static_cast<const uint8_t*>(w); g.bias = bias; g.mult = multiplier; g.shift = shift;
@@ -392,16 +280,14 @@ extern "C" int32_t mi355q_qfc_output_i8(const int8_t* xq, int64_t n, int64_t d, 
   g.zp_x = x_zero_point; g.zp_y = out_zero_point; g.act_min = act_min; g.act_max = act_max; g.kind = w_kind;
   hipStream_t st = as_stream(stream);
 
-  const bool mfma = d % 64 == 0 && reinterpret_cast<uintptr_t>(xq) % 16 == 0 && reinterpret_cast<uintptr_t>(w) % 16 == 0;
-  if (mfma) {
+  if (mfma_route(xq, w, d, 64)) {
     if (x_zero_point != 0) {
       const int32_t st_sums = launch_weight_sums(g.w, w_kind, rows, static_cast<long long>(d), static_cast<int32_t*>(workspace), st);
       if (st_sums != MI355Q_OK) return st_sums;
     }
-    const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(tok_tiles));
-    if (w_kind == MI355Q_CMP_I8) hipLaunchKernelGGL(qfc_out_mfma_kernel<MI355Q_CMP_I8>, grid, dim3(kThreads), 0, st, g);
-    else if (w_kind == MI355Q_CMP_I4) hipLaunchKernelGGL(qfc_out_mfma_kernel<MI355Q_CMP_I4>, grid, dim3(kThreads), 0, st, g);
-    else hipLaunchKernelGGL(qfc_out_mfma_kernel<MI355Q_CMP_I2>, grid, dim3(kThreads), 0, st, g);
+    dispatch_kind(w_kind, [&](auto kind) {
+      hipLaunchKernelGGL(qfc_out_mfma_kernel<decltype(kind)::value>, grid, dim3(kThreads), 0, st, g);
+    });
   } else {      // (the generic kernel subtracts the zero point element by element: no weight sums)
     hipLaunchKernelGGL(qfc_out_generic_kernel, dim3(generic_blocks(n * rows)), dim3(kThreads), 0, st, g);
   }
@@ -414,20 +300,18 @@ extern "C" int32_t mi355q_qfc_output_i16(const int16_t* xq, int64_t n, int64_t d
                                          const int32_t* shift, int64_t mcount, int32_t act_min, int32_t act_max,
                                          int16_t* q_out, void* workspace, size_t workspace_bytes, void* stream) {
   clear_error();
-  const int32_t common = check_common(xq, n, d, w, w_kind, rows, multiplier, shift, mcount, q_out);
-  if (common != 1) return common;
+  if (const int32_t bad = check_common(xq, n, d, w, w_kind, rows, multiplier, shift, mcount, q_out)) return bad;
   if (act_min > act_max || act_min < -32768 || act_max > 32767)
     return fail(MI355Q_BAD_ARG, "activation range [%d, %d] is no range within int16", act_min, act_max);
-  if (d > kMaxD)
-    return fail(MI355Q_UNSUPPORTED, "d = %lld exceeds %d (the int32 planes of the accumulator)", static_cast<long long>(d), kMaxD);
+  if (d > kQfcMaxD)
+    return fail(MI355Q_UNSUPPORTED, "d = %lld exceeds %d (the int32 planes of the accumulator)", static_cast<long long>(d), kQfcMaxD);
   // the weight sums are a term of every accumulator of the MFMA route: the workspace is always required
-  const size_t need = (rows > 0 && d > 0) ? out_workspace(rows) : 0;
-  if (need > 0 && (!workspace || workspace_bytes < need))
-    return fail(MI355Q_BAD_ARG, "workspace of %zu bytes is smaller than the %zu needed", workspace ? workspace_bytes : size_t{0}, need);
+  if (const int32_t bad = check_workspace(workspace, workspace_bytes, (rows > 0 && d > 0) ? wsum_workspace(rows, 1) : 0))
+    return bad;
   if (n == 0 || rows == 0) return MI355Q_OK;
   if (d == 0) return fail(MI355Q_BAD_ARG, "d must be >= 1");
-  const int64_t row_tiles = (rows + BTB - 1) / BTB, tok_tiles = (n + BTA - 1) / BTA;
-  if (row_tiles > 0x7FFFFFFFLL || tok_tiles > 65535) return fail(MI355Q_UNSUPPORTED, "too many tiles for one launch");
+  dim3 grid;
+  if (const int32_t bad = tile_grid<int16_t>(n, rows, &grid)) return bad;
 
   OutArgs g{};
   g.xq = xq; g.w = static_cast<const uint8_t*>(w); g.bias = bias; g.mult = multiplier; g.shift = shift;
@@ -436,14 +320,12 @@ extern "C" int32_t mi355q_qfc_output_i16(const int16_t* xq, int64_t n, int64_t d
   g.act_min = act_min; g.act_max = act_max; g.kind = w_kind;
   hipStream_t st = as_stream(stream);
 
-  const bool mfma = d % 64 == 0 && reinterpret_cast<uintptr_t>(xq) % 16 == 0 && reinterpret_cast<uintptr_t>(w) % 16 == 0;
-  if (mfma) {
+  if (mfma_route(xq, w, d, 64)) {
     const int32_t st_sums = launch_weight_sums(g.w, w_kind, rows, static_cast<long long>(d), static_cast<int32_t*>(workspace), st);
     if (st_sums != MI355Q_OK) return st_sums;
-    const dim3 grid(static_cast<unsigned>(row_tiles), static_cast<unsigned>(tok_tiles));
-    if (w_kind == MI355Q_CMP_I8) hipLaunchKernelGGL(qfc_out16_mfma_kernel<MI355Q_CMP_I8>, grid, dim3(kThreads), 0, st, g);
-    else if (w_kind == MI355Q_CMP_I4) hipLaunchKernelGGL(qfc_out16_mfma_kernel<MI355Q_CMP_I4>, grid, dim3(kThreads), 0, st, g);
-    else hipLaunchKernelGGL(qfc_out16_mfma_kernel<MI355Q_CMP_I2>, grid, dim3(kThreads), 0, st, g);
+    dispatch_kind(w_kind, [&](auto kind) {
+      hipLaunchKernelGGL(qfc_out16_mfma_kernel<decltype(kind)::value>, grid, dim3(kThreads), 0, st, g);
+    });
   } else {
     hipLaunchKernelGGL(qfc_out16_generic_kernel, dim3(generic_blocks(n * rows)), dim3(kThreads), 0, st, g);
   }

@@ -369,3 +369,10 @@ def test_qfc_kernels_use_no_scratch_and_the_int8_matrix_cores(tmp_path):
       assert "v_mfma_i32_16x16x32_i8" in text[k] and "v_mfma_i32_16x16x64_i8" not in text[k], k
     else:
       assert "v_mfma_i32_16x16x64_i8" in text[k] and "v_mfma_i32_16x16x32_i8" not in text[k], k
+  # waves per SIMD as the compiler reports them, per (K step, blockwise): what the kernels had when each held a copy
+  # of the main loop that csrc/qfc_tile.h now holds once (profiles/qfc_unify_isa.txt)
+  floor = {("64", "0"): 3, ("32", "1"): 2, ("64", "1"): 1}
+  for k in kernels:
+    if "qfc_mfma_kernel" in k:
+      occ = re.search(r"^%s:.*?;\s*Occupancy:\s*(\d+)" % re.escape(k), asm, re.M | re.S)
+      assert occ and int(occ.group(1)) >= floor[re.search(r"Li(\d+)ELb([01])E", k).groups()], (k, occ and occ.group(1))

@@ -303,3 +303,10 @@ def test_qfc16_kernels_use_no_scratch_and_the_int8_matrix_cores(tmp_path):
       assert "v_mfma_i32_16x16x64_i8" in text[k] and "v_mfma_i32_16x16x32_i8" not in text[k], k
     if "qfc16_mfma_kernel" in k:      # the split of the activation into its two int8 planes is done in registers
       assert "v_perm_b32" in text[k], k
+  # waves per SIMD as the compiler reports them, per (K step, blockwise): what the kernels had before their policy,
+  # constants and host side moved into csrc/qfc_tile.h (profiles/qfc_unify_isa.txt)
+  floor = {("64", "0"): 3, ("32", "1"): 2, ("64", "1"): 2}
+  for k in kernels:
+    if "qfc16_mfma_kernel" in k:
+      occ = re.search(r"^%s:.*?;\s*Occupancy:\s*(\d+)" % re.escape(k), asm, re.M | re.S)
+      assert occ and int(occ.group(1)) >= floor[re.search(r"Li(\d+)ELb([01])E", k).groups()], (k, occ and occ.group(1))

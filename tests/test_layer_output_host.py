@@ -462,3 +462,9 @@ def test_qfc_out_kernels_use_no_scratch_and_the_int8_matrix_cores(tmp_path):
       assert stores and stores <= ({"global_store_byte"} if "out_mfma" in k else {"global_store_short"}), (k, stores)
     if "qfc_out16_mfma_kernel" in k:
       assert "v_perm_b32" in text[k], k
+  # waves per SIMD as the compiler reports them: what the kernels had before csrc/qfc_tile.h
+  # (profiles/qfc_unify_isa.txt)
+  for k in kernels:
+    if "mfma_kernel" in k:
+      occ = re.search(r"^%s:.*?;\s*Occupancy:\s*(\d+)" % re.escape(k), asm, re.M | re.S)
+      assert occ and int(occ.group(1)) >= 3, (k, occ and occ.group(1))
