@@ -146,6 +146,20 @@ PROTOTYPES = {
                                       c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_conv_patches_nhwc": (c_i32, [c_ptr, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                          c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
+    "mi355q_dwconv_forward_f32": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                          c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
+    "mi355q_dwconv_forward_i8": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i32, c_i32,
+                                         c_i32, c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64,
+                                         c_i64, c_ptr, c_ptr, c_ptr]),
+    "mi355q_dwconv_forward_i16": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i32, c_i32, c_i32, c_i32,
+                                          c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64,
+                                          c_ptr, c_ptr, c_ptr]),
+    "mi355q_dwconv_output_i8": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_i32, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr,
+                                        c_ptr, c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                        c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
+    "mi355q_dwconv_output_i16": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr,
+                                         c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64,
+                                         c_i64, c_i64, c_ptr, c_ptr]),
     "mi355q_sqdiff_cols_workspace_bytes": (c_size, [c_i64, c_i64]),
     "mi355q_sqdiff_cols_f64": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_size, c_ptr]),
     "mi355q_clock_probe": (c_i32, [c_f64, c_ptr, c_ptr]),

@@ -902,10 +902,71 @@ def _conv_2d_ops(m, sg_index: int):
   return out
 
 
+# `depthwise_conv_2d`: DEPTHWISE_CONV_2D ops, executed by a direct convolution (csrc/dwconv.hip)
+_DEPTHWISE_CONV_2D = 4
+_DEPTHWISE_CONV_2D_OPTIONS_TYPE = 2      # DepthwiseConv2DOptions in the BuiltinOptions union
+SKIP_DEPTHWISE_FILTER = "the filter is not a constant float32 [1, KH, KW, O] tensor"
+SKIP_DEPTHWISE_MULTIPLIER = ("the filter's output channels are no multiple of the sample's channels, or the"
+                             " depth_multiplier option is not their ratio")
+SKIP_DEPTHWISE_KIND = "the target filter is not int8"
+SKIP_DEPTHWISE_BLOCKWISE = "the depthwise filter has blockwise scales"
+SKIP_DEPTHWISE_SCALE_AXIS = "the filter's per-channel scales are not along dimension 3"
+SKIP_DEPTHWISE_MISMATCH = "the float op and the target op disagree about padding, strides, dilations or depth multiplier"
+_DEPTHWISE_OPTION_FIELDS = (("padding", "padding", "i8", 0), ("stride_w", "strideW", "i32", 0),
+                            ("stride_h", "strideH", "i32", 0), ("depth_multiplier", "depthMultiplier", "i32", 0),
+                            ("fused_activation_function", "fusedActivationFunction", "i8", 0),
+                            ("dilation_w_factor", "dilationWFactor", "i32", 1),
+                            ("dilation_h_factor", "dilationHFactor", "i32", 1))
+
+
+def depthwise_conv_2d_options(op) -> Optional[dict]:
+  """DepthwiseConv2DOptions of a DEPTHWISE_CONV_2D op as {padding (0 SAME, 1 VALID), stride_w, stride_h,
+  depth_multiplier, fused_activation_function, dilation_w_factor, dilation_h_factor}, in the schema's field order (ids
+  0 to 6), read as conv_2d_options reads Conv2DOptions: from an OpaqueTableT by field id with the schema's defaults
+  for absent fields (0, and 1 for the dilations; a depth_multiplier of 0 says nothing, converters leave it to the
+  shapes), or from a decoded object with the generated API's attribute names; an op without options has every
+  default. None when the op carries the options of another op type."""
+  o = op.builtinOptions
+  if o is None:
+    return {name: default for name, _, _, default in _DEPTHWISE_OPTION_FIELDS}
+  if isinstance(o, tfl_flatbuffer.OpaqueTableT):
+    if int(getattr(op, "builtinOptionsType", 0) or 0) != _DEPTHWISE_CONV_2D_OPTIONS_TYPE:
+      return None
+    return {name: int(o.scalar(i, code, default)) for i, (name, _, code, default) in enumerate(_DEPTHWISE_OPTION_FIELDS)}
+  if not hasattr(o, "depthMultiplier"):
+    return None
+  out = {}
+  for name, attr, _, default in _DEPTHWISE_OPTION_FIELDS:
+    v = getattr(o, attr, None)
+    out[name] = default if v is None else int(v)
+  return out
+
+
+def _depthwise_option(op, field: str) -> int:
+  """_conv_option for a DEPTHWISE_CONV_2D."""
+  if field != "fusedActivationFunction":
+    return 0
+  options = depthwise_conv_2d_options(op)
+  return -1 if options is None else options["fused_activation_function"]
+
+
+def _depthwise_conv_2d_ops(m, sg_index: int):
+  """(op, input 0 name, filter tensor, output name) of every DEPTHWISE_CONV_2D op of a subgraph."""
+  sg = m.subgraphs[sg_index]
+  out = []
+  for op in sg.operators or []:
+    if (int(m.operatorCodes[op.opcodeIndex].builtinCode) != _DEPTHWISE_CONV_2D or len(op.inputs) < 2 or op.inputs[0] < 0
+        or op.inputs[1] < 0):
+      continue
+    out.append((op, schema.tensor_name(sg.tensors[op.inputs[0]]), sg.tensors[op.inputs[1]],
+                schema.tensor_name(sg.tensors[op.outputs[0]])))
+  return out
+
+
 def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray,
                  option=_fc_option):
   """An OutputPlan, or the FINAL_SKIP_* reason there is none. `option(op, field)` reads an op's options
-  (_conv_option for a CONV_2D, whose FC-only fields are default)."""
+  (_conv_option for a CONV_2D and _depthwise_option for a DEPTHWISE_CONV_2D, whose FC-only fields are default)."""
   from . import ops
   if option(fc, "weightsFormat") != 0 or option(ref_op, "weightsFormat") != 0:
     return FINAL_SKIP_WEIGHTS_FORMAT
@@ -1013,6 +1074,45 @@ class LayerExecutionKernels:
     image = torch.arange(n * patch_rows, device=x.device) // patch_rows
     return q.view(x.shape), scale[image]
 
+  # (`depthwise_conv_2d`: x [N, H, W, C] float32 / int8 / int16; rows first .. first + count - 1 of the N OH OW output
+  # rows as [count, O]; `kernel` (KH, KW); the filter is [KH KW, O], the stored bytes of TFLite's [1, KH, KW, O])
+  def depthwise_float(self, x, w, kernel: tuple, depth_multiplier: int, strides: tuple, dilations: tuple, padding: str,
+                      first: int, count: int):
+    """float32 [count, O]: the float op's pre-bias product, every product and sum rounded, taps in order
+    (ops.dwconv_forward on float32)."""
+    from . import ops
+    return ops.dwconv_forward(x, w, kernel[0], kernel[1], strides, dilations, padding, depth_multiplier, first=first,
+                              count=count)
+
+  def depthwise_forward(self, xq, x_scale, x_zero_point: int, target, kernel: tuple, depth_multiplier: int, strides: tuple,
+                        dilations: tuple, padding: str, first: int, count: int):
+    """float32 [count, O] of int8 activations, `x_scale` 1 or N entries (one per image) (ops.dwconv_forward)."""
+    from . import ops
+    return ops.dwconv_forward(xq, target, kernel[0], kernel[1], strides, dilations, padding, depth_multiplier,
+                              x_scale=x_scale, x_zero_point=x_zero_point, first=first, count=count)
+
+  def depthwise_forward16(self, xq, x_scale, target, kernel: tuple, depth_multiplier: int, strides: tuple, dilations: tuple,
+                          padding: str, first: int, count: int):
+    """float32 [count, O] of int16 activations (ops.dwconv_forward)."""
+    from . import ops
+    return ops.dwconv_forward(xq, target, kernel[0], kernel[1], strides, dilations, padding, depth_multiplier,
+                              x_scale=x_scale, first=first, count=count)
+
+  def depthwise_output(self, xq, x_zero_point: int, target, kernel: tuple, depth_multiplier: int, strides: tuple,
+                       dilations: tuple, padding: str, bias, multiplier, shift, out_zero_point: int, act_min: int,
+                       act_max: int, first: int, count: int):
+    """int8 [count, O]: what the static int8 op stores (ops.dwconv_output)."""
+    from . import ops
+    return ops.dwconv_output(xq, x_zero_point, target, kernel[0], kernel[1], strides, dilations, padding, bias, multiplier,
+                             shift, out_zero_point, act_min, act_max, depth_multiplier, first, count)
+
+  def depthwise_output16(self, xq, target, kernel: tuple, depth_multiplier: int, strides: tuple, dilations: tuple,
+                         padding: str, bias, multiplier, shift, act_min: int, act_max: int, first: int, count: int):
+    """int16 [count, O]: what the static int16-activation op stores (ops.dwconv_output_i16)."""
+    from . import ops
+    return ops.dwconv_output_i16(xq, target, kernel[0], kernel[1], strides, dilations, padding, bias, multiplier, shift,
+                                 act_min, act_max, depth_multiplier, first, count)
+
   def transform(self, x, kind: str, multiplier, hadamard_size: int):
     """The inserted op's own map on rows of length d: x * multiplier, or x R with R = blockdiag(H_h / sqrt(h))."""
     from . import ops
@@ -1116,6 +1216,8 @@ class LayerExecutionComparison(LayerOutputComparison):
   `final_per_channel_error`, or `final_skipped` with the reason there are none;
   with `conv_2d` also `op` ("FULLY_CONNECTED" or "CONV_2D"), and for a CONV_2D (rows = O, d = KH KW I, tokens = patch
   rows) `kernel`, `strides`, `dilations`, `padding` and `output_hw`;
+  with `depthwise_conv_2d` also `op` (then also "DEPTHWISE_CONV_2D"), and for such an op the keys of a CONV_2D entry
+  (rows = O, d = KH KW, tokens = output rows) and `depth_multiplier`;
   `skipped[name]` is the reason an op was not computed."""
 
   def as_dict(self) -> dict:
@@ -1140,7 +1242,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                             follow_input_transforms: bool = False,
                             int16_activations: bool = False,
                             quantized_outputs: bool = False,
-                            conv_2d: bool = False) -> LayerExecutionComparison:
+                            conv_2d: bool = False,
+                            depthwise_conv_2d: bool = False) -> LayerExecutionComparison:
   """Executes every quantized FULLY_CONNECTED op in integers on the calibration samples and compares it with the
   float model's product, for every op of the float model with a constant 2-D float32 weight [rows, d] whose input 0
   is in `samples` (the {tensor name: array or device tensor} maps calibrate() takes; tensors of any rank are rows of
@@ -1208,6 +1311,26 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
   `kernel` [KH, KW], `strides` and `dilations` [h, w], `padding` ("SAME" / "VALID") and `output_hw` (of the first
   sample). Further skip reasons: SKIP_CONV_FILTER, SKIP_CONV_GROUPS (I differs from the sample's channels),
   SKIP_CONV_OPTIONS, SKIP_CONV_GEOMETRY, SKIP_CONV_BLOCKWISE, and SKIP_SAMPLE_SHAPE for a sample that is not rank 4.
+  Without the keyword nothing changes.
+
+  With `depthwise_conv_2d` every DEPTHWISE_CONV_2D op of the float model is executed as well, whose filter is a
+  constant float32 [1, KH, KW, O] and whose input 0 has samples of rank 4, [N, H, W, C], with O a multiple of C: the
+  depth multiplier is M = O / C and output channel oc reads input channel oc // M. Such a filter's reduction (its
+  KH KW taps) is not contiguous per output channel and every output channel reads one input channel, so there are
+  no patch rows and no shared product: the op is a direct convolution (ops.dwconv_forward, ops.dwconv_output,
+  ops.dwconv_output_i16), in chunks of at most 4096 of its N OH OW output rows. The graph reading (the target filter,
+  integer or behind a DEQUANTIZE; the activation's type and so the mode; the QUANTIZE producer) is CONV_2D's; the
+  filter is int8 with scales per tensor or per channel along dimension 3. Y is the float32 loop
+  (((0 + p_0) + p_1) ...) over the taps inside the image in ascending (kh, kw) order, p = fl32(x w), and under
+  "weight_only" Yq is the same loop on the dequantized filter. "static": the sample is quantized once (8 or 16
+  bits); a tap outside the image is skipped, which is what a pad element q(0.0) = zp_x adds. "dynamic": one scale per
+  batch element, every image quantized as a whole. With `quantized_outputs` the epilogue above runs on the
+  accumulator, the fused activation read from DepthwiseConv2DOptions (depthwise_conv_2d_options). An entry carries
+  the keys of a conv entry with `op` = "DEPTHWISE_CONV_2D", `rows` = O, `d` = KH KW, `tokens` = the number of output
+  rows, and `depth_multiplier`; EVERY entry carries `op` whenever either conv keyword is on. Further skip reasons:
+  SKIP_DEPTHWISE_FILTER, SKIP_DEPTHWISE_MULTIPLIER (O is no multiple of C, or a non-zero depth_multiplier option
+  that is not O / C), SKIP_DEPTHWISE_KIND, SKIP_DEPTHWISE_BLOCKWISE, SKIP_DEPTHWISE_SCALE_AXIS,
+  SKIP_DEPTHWISE_MISMATCH (the two ops' options differ); the reasons of CONV_2D that apply keep their texts.
   Without the keyword nothing changes.
   """
   kernels = kernels or LayerExecutionKernels()
@@ -1377,14 +1500,14 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                      final_per_channel_error=f_channel)
       elif final is not None:
         entry["final_skipped"] = final
-    if conv_2d:
+    if conv_2d or depthwise_conv_2d:
       out.results[y_name]["op"] = "FULLY_CONNECTED"
-  if not conv_2d:
+  if not (conv_2d or depthwise_conv_2d):
     return out
 
-  # ---- CONV_2D: the same product on patch rows (the docstring's last section)
+  # ---- CONV_2D: the same product on patch rows (the docstring's section on `conv_2d`)
   from . import ops
-  for ref_op, x_name, w, y_name in _conv_2d_ops(ref, sg_ref):
+  for ref_op, x_name, w, y_name in (_conv_2d_ops(ref, sg_ref) if conv_2d else []):
     w_name = schema.tensor_name(w)
     if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
         or min(int(v) for v in w.shape) < 1):
@@ -1547,6 +1670,194 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
         "op": "CONV_2D", "weight": w_name, "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
         "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations), "padding": padding,
         "output_hw": [shapes[0][0], shapes[0][1]],
+        "signal": signal, "error": error, "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
+        "per_channel_error": per_channel}
+    if follow_input_transforms:
+      entry.update(input_transform=TRANSFORM_NONE, hadamard_size=0)
+    if int16_activations:
+      entry["activation_bits"] = activation_bits
+    if quantized_outputs:
+      entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
+      if isinstance(final, OutputPlan):
+        f_diff, f_ref = kernels.host(final_sums)
+        f_channel = np.asarray(f_diff, np.float64) / tokens
+        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
+        f_mse = f_error / rows
+        entry.update(fused_activation=ops.FUSED_ACTIVATION_NAMES[final.fused], final_signal=f_signal,
+                     final_error=f_error, final_output_mse=f_mse, final_output_snr=(f_signal / rows) / (f_mse + 1e-9),
+                     final_per_channel_error=f_channel)
+      elif final is not None:
+        entry["final_skipped"] = final
+  if not depthwise_conv_2d:
+    return out
+
+  # ---- DEPTHWISE_CONV_2D: a direct convolution, no patch rows (the docstring's section on `depthwise_conv_2d`)
+  for ref_op, x_name, w, y_name in _depthwise_conv_2d_ops(ref, sg_ref):
+    w_name = schema.tensor_name(w)
+    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
+        or int(w.shape[0]) != 1 or min(int(v) for v in w.shape) < 1):
+      out.skipped[y_name] = SKIP_DEPTHWISE_FILTER
+      continue
+    _, kh, kw, rows = (int(v) for v in w.shape)
+    d = kh * kw
+    conv = producer_op.get(y_name)
+    if (conv is None or code(conv) != _DEPTHWISE_CONV_2D or len(conv.inputs) < 2 or conv.inputs[0] < 0
+        or conv.inputs[1] < 0):
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    options, float_options = depthwise_conv_2d_options(conv), depthwise_conv_2d_options(ref_op)
+    geometry = ("padding", "stride_h", "stride_w", "dilation_h_factor", "dilation_w_factor")
+    if options is None or float_options is None:
+      out.skipped[y_name] = SKIP_CONV_OPTIONS
+      continue
+    if any(options[k] != float_options[k] for k in geometry + ("depth_multiplier",)):
+      out.skipped[y_name] = SKIP_DEPTHWISE_MISMATCH
+      continue
+    if options["padding"] not in ops.CONV_PADDING_NAMES or min(options[k] for k in geometry[1:]) < 1:
+      out.skipped[y_name] = SKIP_CONV_OPTIONS
+      continue
+    strides, dilations = (options["stride_h"], options["stride_w"]), (options["dilation_h_factor"], options["dilation_w_factor"])
+    padding = ops.CONV_PADDING_NAMES[options["padding"]]
+    # ---- the filter the target op reads: the integer constant itself, or a DEQUANTIZE of it
+    read = tgt_sg.tensors[conv.inputs[1]]
+    target, through_dequantize = read, False
+    if not _has_data(tgt.buffers, read):
+      deq = producers.get(int(conv.inputs[1]))
+      if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
+        out.skipped[y_name] = SKIP_TARGET
+        continue
+      target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
+    if schema.tensor_name(target) != w_name or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if target.type in (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16):
+      out.skipped[y_name] = SKIP_FLOAT_TARGET
+      continue
+    # ---- the activation it reads (as for CONV_2D: an op behind an inserted op is skipped)
+    x_in = tgt_sg.tensors[conv.inputs[0]]
+    if x_in.type == schema.TensorType.INT16 and not int16_activations:
+      out.skipped[y_name] = SKIP_INT16
+      continue
+    x_quant, activation_bits = None, None
+    if x_in.type in (schema.TensorType.INT8, schema.TensorType.INT16):
+      q = x_in.quantization
+      source = name(conv.inputs[0])
+      quantize = producers.get(int(conv.inputs[0]))
+      if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
+        source = name(quantize.inputs[0])
+      if q is None or q.scale is None or len(q.scale) != 1 or source != x_name or through_dequantize:
+        out.skipped[y_name] = SKIP_INPUT
+        continue
+      zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
+      activation_bits = 16 if x_in.type == schema.TensorType.INT16 else 8
+      if (activation_bits == 16 and zero_point != 0) or not -128 <= zero_point <= 127:
+        out.skipped[y_name] = SKIP_INPUT
+        continue
+      x_quant = (float(np.float32(q.scale[0])), zero_point)
+      mode = MODE_STATIC
+    elif x_in.type == schema.TensorType.FLOAT32 and name(conv.inputs[0]) == x_name:
+      mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
+    else:
+      out.skipped[y_name] = SKIP_INPUT
+      continue
+    # ---- the filter as a [KH KW, O] constant: the stored bytes of [1, KH, KW, O]
+    values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
+    plan = _target_plan(w_name, values, tgt, target)
+    if plan is None or not plan.dequantized:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    if plan.kind != "i8":
+      out.skipped[y_name] = SKIP_DEPTHWISE_KIND
+      continue
+    if plan.scale is None:
+      out.skipped[y_name] = SKIP_DEPTHWISE_BLOCKWISE
+      continue
+    if (not (plan.channels == 1 or (plan.channels == rows and plan.inner == 1))
+        or np.asarray(plan.scale).size != plan.channels):      # (O scales along dimension 0, of size 1, read as one)
+      out.skipped[y_name] = SKIP_DEPTHWISE_SCALE_AXIS
+      continue
+    if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
+      out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
+      continue
+    present = [s[x_name] for s in samples if x_name in s]
+    if not present:
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    if any(len(v.shape) != 4 for v in present):
+      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
+      continue
+    channels = int(present[0].shape[3])
+    if (channels < 1 or any(int(v.shape[3]) != channels for v in present) or rows % channels
+        or options["depth_multiplier"] not in (0, rows // channels)):
+      out.skipped[y_name] = SKIP_DEPTHWISE_MULTIPLIER
+      continue
+    multiplier = rows // channels
+    try:
+      if d > ops.DWCONV_MAX_TAPS:
+        raise ValueError("taps")
+      shapes = [ops.conv_geometry(int(v.shape[1]), int(v.shape[2]), kh, kw, strides, dilations, padding) for v in present
+                if int(v.shape[0]) > 0]
+    except ValueError:
+      out.skipped[y_name] = SKIP_CONV_GEOMETRY
+      continue
+    if not shapes:            # (every sample of the input was empty)
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    w_dev = kernels.weight(values, d, rows)
+    t_dev = kernels.target(plan)
+    dq_dev = kernels.dequantized(t_dev, d, rows) if mode == MODE_WEIGHT_ONLY else None
+    final, final_sums, bias_dev, float_bias_dev = None, None, None, None
+    if quantized_outputs and mode == MODE_STATIC:
+      final = _output_plan(ref, ref.subgraphs[sg_ref], ref_op, tgt, tgt_sg, conv, rows, activation_bits, x_quant[0],
+                           plan.scale, option=_depthwise_option)
+    if isinstance(final, OutputPlan):
+      bias_dev = None if final.bias is None else kernels.bias(final.bias)
+      float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
+    sums, tokens = None, 0
+    where = (kh, kw), multiplier, strides, dilations, padding
+    for value in present:
+      if int(value.shape[0]) == 0:
+        continue
+      x = kernels.sample4d(value)
+      oh, ow, _, _ = ops.conv_geometry(int(x.shape[1]), int(x.shape[2]), kh, kw, strides, dilations, padding)
+      n = int(x.shape[0]) * oh * ow
+      # the sample is quantized ONCE; a tap outside the image is skipped, which is what a pad element q(0.0) = zp_x adds
+      if mode == MODE_DYNAMIC:
+        xq_all, x_scale = kernels.quantize_dynamic_images(x, 1)      # (one scale per image)
+      elif mode == MODE_STATIC and activation_bits == 16:
+        xq_all, x_scale = kernels.quantize_static16(x, x_quant[0])
+      elif mode == MODE_STATIC:
+        xq_all, x_scale = kernels.quantize_static(x, *x_quant)
+      for first in range(0, n, EXECUTION_CHUNK_ROWS):
+        count = min(EXECUTION_CHUNK_ROWS, n - first)
+        y = kernels.depthwise_float(x, w_dev, *where, first, count)
+        if mode == MODE_WEIGHT_ONLY:
+          yq = kernels.depthwise_float(x, dq_dev, *where, first, count)
+        elif mode == MODE_DYNAMIC:
+          yq = kernels.depthwise_forward(xq_all, x_scale, 0, t_dev, *where, first, count)
+        elif activation_bits == 16:
+          yq = kernels.depthwise_forward16(xq_all, x_scale, t_dev, *where, first, count)
+        else:
+          yq = kernels.depthwise_forward(xq_all, x_scale, x_quant[1], t_dev, *where, first, count)
+        sums = kernels.sqdiff(yq, y, sums)
+        if isinstance(final, OutputPlan):
+          if activation_bits == 16:
+            q_out = kernels.depthwise_output16(xq_all, t_dev, *where, bias_dev, final.multiplier, final.shift,
+                                               final.act_min, final.act_max, first, count)
+          else:
+            q_out = kernels.depthwise_output(xq_all, x_quant[1], t_dev, *where, bias_dev, final.multiplier, final.shift,
+                                             final.zero_point, final.act_min, final.act_max, first, count)
+          final_sums = kernels.sqdiff(kernels.dequantize_output(q_out, final.scale, final.zero_point),
+                                      kernels.reference_output(y, float_bias_dev, final.float_fused), final_sums)
+      tokens += n
+    sq_diff, sq_ref = kernels.host(sums)
+    per_channel = np.asarray(sq_diff, np.float64) / tokens
+    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
+    mse = error / rows
+    entry = out.results[y_name] = {
+        "op": "DEPTHWISE_CONV_2D", "weight": w_name, "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
+        "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations), "padding": padding,
+        "output_hw": [shapes[0][0], shapes[0][1]], "depth_multiplier": multiplier,
         "signal": signal, "error": error, "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
         "per_channel_error": per_channel}
     if follow_input_transforms:

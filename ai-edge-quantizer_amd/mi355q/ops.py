@@ -1377,6 +1377,180 @@ def conv_patches(x: torch.Tensor, kh: int, kw: int, stride, dilation, padding, p
   return out
 
 
+# (include/mi355q.h, "Direct depthwise convolution")
+DWCONV_MAX_TAPS = 65536
+
+
+def _dwconv_geometry(who: str, x, dtypes, kh: int, kw: int, depth_multiplier: int, stride, dilation, padding, first: int,
+                     count):
+  """The argument checks the depthwise entries share; returns the integers of the C call's geometry, in its order
+  after (N, H, W, C): (n, h, w, c), (kh, kw, m), (sh, sw, dh, dw, top, left, oh, ow, first, count), and O = C M."""
+  if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in dtypes:
+    names = " or ".join(str(t).replace("torch.", "") for t in dtypes)
+    raise TypeError(f"{who}: expected an {names} device tensor, got {getattr(x, 'dtype', type(x))}"
+                    f" on {getattr(x, 'device', 'the host')}")
+  if x.dim() != 4:
+    raise ValueError(f"{who}: expected an [N, H, W, C] tensor, got {tuple(x.shape)}")
+  n_img, h, w, c = (int(v) for v in x.shape)
+  kh, kw, m = int(kh), int(kw), int(depth_multiplier)
+  (sh, sw), (dh, dw) = _pair(stride, "stride"), _pair(dilation, "dilation")
+  if min(n_img, h, w, c) < 1:
+    raise ValueError(f"{who}: every dimension of x must be positive, got {tuple(x.shape)}")
+  if m < 1:
+    raise ValueError(f"{who}: the depth multiplier must be positive (got {m})")
+  oh, ow, top, left = conv_geometry(h, w, kh, kw, (sh, sw), (dh, dw), padding)
+  if kh * kw > DWCONV_MAX_TAPS:
+    raise ValueError(f"{who}: {kh} x {kw} taps exceed {DWCONV_MAX_TAPS}")
+  rows_all = n_img * oh * ow
+  if rows_all > 0x7FFFFFFF or c * m > 0x7FFFFFFF:
+    raise ValueError(f"{who}: {rows_all} output rows of {c * m} channels exceed INT32_MAX")
+  first = int(first)
+  count = rows_all - first if count is None else int(count)
+  if first < 0 or count < 0 or first + count > rows_all:
+    raise ValueError(f"{who}: rows [{first}, {first} + {count}) are outside the {rows_all} output rows")
+  return (n_img, h, w, c), (kh, kw, m), (sh, sw, dh, dw, top, left, oh, ow, first, count), c * m
+
+
+def _dwconv_filter(who: str, target: CompareTarget, taps: int, o: int) -> None:
+  """An int8 filter [KH, KW, O] with per-tensor scales, or per-channel scales along its last dimension."""
+  if not isinstance(target, CompareTarget) or target.kind != "i8":
+    raise ValueError(f"{who} needs an i8 filter (a CompareTarget), got {getattr(target, 'kind', type(target))!r}")
+  if target.n != taps * o or target.data.dtype != torch.int8 or not target.data.is_cuda:
+    raise ValueError(f"{who}: the filter has {target.n} elements, expected {taps} x {o} int8 on the device")
+  if target.zero_point is not None and bool(torch.any(target.zero_point != 0)):
+    raise ValueError("the weight's zero point must be 0")
+  if not (target.channels == 1 or (target.channels == o and target.inner == 1)):
+    raise ValueError(f"{who}: scale view ({target.channels} channels, inner {target.inner}) is neither per tensor nor per"
+                     f" channel along the last dimension of a [{taps}, {o}] filter")
+  if target.scale.numel() != target.channels:
+    raise ValueError("scale must have one entry per channel")
+
+
+def dwconv_forward(x: torch.Tensor, w, kh: int, kw: int, stride, dilation, padding, depth_multiplier: int = 1,
+                   x_scale: torch.Tensor | None = None, x_zero_point: int = 0, first: int = 0, count: int | None = None,
+                   want_acc: bool = False):
+  """The DEPTHWISE_CONV_2D product of an NHWC activation x [N, H, W, C] on the device and a filter [KH, KW, O]
+  (O = C depth_multiplier, the stored bytes of TFLite's [1, KH, KW, O]; output channel oc reads input channel
+  oc // depth_multiplier), as float32 [count, O]: rows first .. first + count - 1 of the N OH OW output rows (default:
+  all from `first` on), the geometry conv_geometry's; a tap outside the image adds nothing. By the dtype of x:
+    float32  `w` a float32 device tensor of KH KW O elements: y = (((0 + p_0) + p_1) ...), p = fl32(x w), taps in
+             ascending (kh, kw) order, no FMA: the bits of a NumPy float32 loop in that order;
+    int8     `w` a CompareTarget of kind i8 (per tensor, or per channel along the last dimension), `x_scale` float32
+             with 1 or N entries (one per IMAGE), `x_zero_point` in int8:
+             y = float(Sum (x - zp_x) q_w) * (x_scale * w_scale), the accumulator exact in int32;
+    int16    as int8 without a zero point: the accumulator exact in int64 and
+             y = float32(float64(acc) * float64(x_scale * w_scale)).
+  Returns y, or (y, acc int32 / int64 [count, O]) with `want_acc` (integer activations only). The pre-bias product.
+  include/mi355q.h, "Direct depthwise convolution". Does not synchronize."""
+  rt.require_gpu()
+  who = "dwconv_forward"
+  (n_img, h, wd, c), (kh, kw, m), geo, o = _dwconv_geometry(who, x, (torch.float32, torch.int8, torch.int16), kh, kw,
+                                                            depth_multiplier, stride, dilation, padding, first, count)
+  count = geo[-1]
+  if not x.is_contiguous():
+    x = x.contiguous()
+  L = _ffi.lib()
+  y = rt.empty((count, o), torch.float32)
+  if x.dtype == torch.float32:
+    if want_acc or x_scale is not None or int(x_zero_point) != 0:
+      raise ValueError(f"{who}: a float32 activation takes no x_scale, x_zero_point or want_acc")
+    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32 or w.numel() != kh * kw * o:
+      raise TypeError(f"{who}: expected a float32 device filter of {kh} x {kw} x {o} elements, got"
+                      f" {getattr(w, 'dtype', type(w))} {tuple(getattr(w, 'shape', ()))}")
+    w = w if w.is_contiguous() else w.contiguous()
+    _ffi.check(L.mi355q_dwconv_forward_f32(rt.ptr(x), n_img, h, wd, c, rt.ptr(w), kh, kw, m, *geo, rt.ptr(y),
+                                           rt.stream_ptr()))
+    return y
+  _dwconv_filter(who, w, kh * kw, o)
+  if x_scale is None:
+    raise ValueError(f"{who}: an integer activation needs x_scale")
+  x_scale = _f32(x_scale).view(-1)
+  if x_scale.numel() not in (1, n_img):
+    raise ValueError(f"{who}: x_scale needs 1 or N = {n_img} entries (got {x_scale.numel()})")
+  if x.dtype == torch.int8:
+    if not -128 <= int(x_zero_point) <= 127:
+      raise ValueError(f"{who}: x_zero_point {x_zero_point} is outside int8")
+    acc = rt.empty((count, o), torch.int32) if want_acc else None
+    _ffi.check(L.mi355q_dwconv_forward_i8(rt.ptr(x), n_img, h, wd, c, rt.ptr(x_scale), x_scale.numel(), int(x_zero_point),
+                                          rt.ptr(w.data), COMPARE_KINDS[w.kind], kh, kw, m, rt.ptr(w.scale),
+                                          w.scale.numel(), *geo, rt.ptr(y), rt.ptr(acc), rt.stream_ptr()))
+  else:
+    if int(x_zero_point) != 0:
+      raise ValueError(f"{who}: an int16 activation has no zero point")
+    acc = rt.empty((count, o), torch.int64) if want_acc else None
+    _ffi.check(L.mi355q_dwconv_forward_i16(rt.ptr(x), n_img, h, wd, c, rt.ptr(x_scale), x_scale.numel(), rt.ptr(w.data),
+                                           COMPARE_KINDS[w.kind], kh, kw, m, rt.ptr(w.scale), w.scale.numel(), *geo,
+                                           rt.ptr(y), rt.ptr(acc), rt.stream_ptr()))
+  return (y, acc) if want_acc else y
+
+
+def _dwconv_bias(who: str, bias, o: int, bias_dtype):
+  if bias is None:
+    return None
+  if not isinstance(bias, torch.Tensor):
+    bias = rt.to_device(np.ascontiguousarray(np.asarray(bias).reshape(-1)))
+  if bias.dtype != bias_dtype or not bias.is_cuda or bias.numel() != o:
+    name = str(bias_dtype).replace("torch.", "")
+    raise TypeError(f"{who}: the bias must be {name} with {o} entries, got {bias.dtype} with {bias.numel()}")
+  return bias.contiguous().view(-1)
+
+
+def dwconv_output(x: torch.Tensor, x_zero_point: int, target: CompareTarget, kh: int, kw: int, stride, dilation, padding,
+                  bias, multiplier, shift, out_zero_point: int, act_min: int, act_max: int, depth_multiplier: int = 1,
+                  first: int = 0, count: int | None = None) -> torch.Tensor:
+  """What a static int8 DEPTHWISE_CONV_2D op stores: int8 [count, O] =
+  clamp(mbqm32(sat32(acc + bias), M, s) + out_zero_point, act_min, act_max) of dwconv_forward's int32 accumulator,
+  with the arithmetic and the argument forms of qfc_output (`bias` None or int32 [O]; `multiplier` / `shift` host tables
+  of 1 or O entries, or qfc_multipliers' result with `shift` None). Only the stored tensor is written. Does not
+  synchronize."""
+  rt.require_gpu()
+  who = "dwconv_output"
+  (n_img, h, wd, c), (kh, kw, m), geo, o = _dwconv_geometry(who, x, (torch.int8,), kh, kw, depth_multiplier, stride,
+                                                            dilation, padding, first, count)
+  _dwconv_filter(who, target, kh * kw, o)
+  bias = _dwconv_bias(who, bias, o, torch.int32)
+  tables = _qfc_output_tables(who, multiplier, shift, o, 8)
+  for what, v in (("x_zero_point", x_zero_point), ("out_zero_point", out_zero_point)):
+    if not -128 <= int(v) <= 127:
+      raise ValueError(f"{who}: {what} {v} is outside int8")
+  if not -128 <= int(act_min) <= int(act_max) <= 127:
+    raise ValueError(f"{who}: [{act_min}, {act_max}] is no range within int8")
+  if not x.is_contiguous():
+    x = x.contiguous()
+  q = rt.empty((geo[-1], o), torch.int8)
+  _ffi.check(_ffi.lib().mi355q_dwconv_output_i8(rt.ptr(x), n_img, h, wd, c, int(x_zero_point), rt.ptr(target.data),
+                                                COMPARE_KINDS[target.kind], kh, kw, m, rt.ptr(bias),
+                                                rt.ptr(tables.multiplier), rt.ptr(tables.shift), tables.multiplier.numel(),
+                                                int(out_zero_point), int(act_min), int(act_max), *geo, rt.ptr(q),
+                                                rt.stream_ptr()))
+  return q
+
+
+def dwconv_output_i16(x: torch.Tensor, target: CompareTarget, kh: int, kw: int, stride, dilation, padding, bias,
+                      multiplier, shift, act_min: int, act_max: int, depth_multiplier: int = 1, first: int = 0,
+                      count: int | None = None) -> torch.Tensor:
+  """What a static int16-activation DEPTHWISE_CONV_2D op stores: int16 [count, O], qfc_output_i16's arithmetic on
+  dwconv_forward's int64 accumulator (`bias` None or int64 [O]; shifts in [-31, 14]; no zero points). Does not
+  synchronize."""
+  rt.require_gpu()
+  who = "dwconv_output_i16"
+  (n_img, h, wd, c), (kh, kw, m), geo, o = _dwconv_geometry(who, x, (torch.int16,), kh, kw, depth_multiplier, stride,
+                                                            dilation, padding, first, count)
+  _dwconv_filter(who, target, kh * kw, o)
+  bias = _dwconv_bias(who, bias, o, torch.int64)
+  tables = _qfc_output_tables(who, multiplier, shift, o, 16)
+  if not -32768 <= int(act_min) <= int(act_max) <= 32767:
+    raise ValueError(f"{who}: [{act_min}, {act_max}] is no range within int16")
+  if not x.is_contiguous():
+    x = x.contiguous()
+  q = rt.empty((geo[-1], o), torch.int16)
+  _ffi.check(_ffi.lib().mi355q_dwconv_output_i16(rt.ptr(x), n_img, h, wd, c, rt.ptr(target.data), COMPARE_KINDS[target.kind],
+                                                 kh, kw, m, rt.ptr(bias), rt.ptr(tables.multiplier), rt.ptr(tables.shift),
+                                                 tables.multiplier.numel(), int(act_min), int(act_max), *geo, rt.ptr(q),
+                                                 rt.stream_ptr()))
+  return q
+
+
 def sqdiff_cols(a: torch.Tensor, b: torch.Tensor, out: tuple | None = None):
   """(Sum_t (a - b)^2, Sum_t b^2) per column of float32 [n, cols] device tensors, float64 [cols] each, added in a
   fixed order (the same bits in every run). With `out` = an earlier result the sums are added onto it in place and

@@ -249,7 +249,8 @@ class Quantizer:
                                follow_input_transforms: bool = False,
                                int16_activations: bool = False,
                                quantized_outputs: bool = False,
-                               conv_2d: bool = False) -> model_validator.LayerExecutionComparison:
+                               conv_2d: bool = False,
+                               depthwise_conv_2d: bool = False) -> model_validator.LayerExecutionComparison:
     """Executes every quantized FULLY_CONNECTED op of the last quantize() result in integers on the calibration
     samples and compares it with the float product: error = (1/n) ||Yq - Y||^2 per op with its signal, MSE, SNR,
     per-channel errors, token count and mode (model_validator.compare_layer_execution). Unlike
@@ -267,7 +268,9 @@ class Quantizer:
     gains `output_bits`, and such an op `fused_activation` and the `final_*` figures, or `final_skipped` with the
     reason. With `conv_2d` every CONV_2D op is executed too, as the same integer product on the patch rows of its
     rank-4 samples (ops.conv_patches): every entry gains `op`, and a conv entry `kernel`, `strides`, `dilations`,
-    `padding` and `output_hw`, with `rows` the output channels, `d` = KH KW I and `tokens` the patch rows."""
+    `padding` and `output_hw`, with `rows` the output channels, `d` = KH KW I and `tokens` the patch rows. With
+    `depthwise_conv_2d` every DEPTHWISE_CONV_2D op is executed too, by a direct convolution (ops.dwconv_forward): an
+    entry has the keys of a conv entry with `op` = "DEPTHWISE_CONV_2D", `d` = KH KW, and `depth_multiplier`."""
     quantized_model = self._result.quantized_model
     if quantized_model is None:
       raise ValueError("No quantized model available to validate.")
@@ -275,7 +278,8 @@ class Quantizer:
     results = model_validator.compare_layer_execution(self.float_model, bytes(quantized_model), samples, signature_key,
                                                       follow_input_transforms=follow_input_transforms,
                                                       int16_activations=int16_activations,
-                                                      quantized_outputs=quantized_outputs, conv_2d=conv_2d)
+                                                      quantized_outputs=quantized_outputs, conv_2d=conv_2d,
+                                                      depthwise_conv_2d=depthwise_conv_2d)
     if save_folder:
       if model_name is None:
         model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"

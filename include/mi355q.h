@@ -1172,6 +1172,112 @@ int32_t mi355q_conv_patches_nhwc(const void* x, int32_t elem_bytes, int64_t N, i
                                  int32_t pad_top, int32_t pad_left, int64_t OH, int64_t OW, int64_t first_row,
                                  int64_t row_count, const void* pad_element, void* out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Direct depthwise convolution (csrc/dwconv.hip): the DEPTHWISE_CONV_2D op on
+ * an NHWC activation, in float32 and in integers. A TFLite depthwise filter is
+ * [1, KH, KW, O]: the reduction of an output channel is its KH KW taps alone,
+ * they are NOT contiguous, and every output channel reads ONE input channel, so
+ * neither the patch gather above nor a shared GEMM applies. The arithmetic is
+ * this library's own definition, modelled on LiteRT's DEPTHWISE_CONV_2D;
+ * agreement with LiteRT's kernels has not been checked, the claim is bit
+ * equality with the statement below.
+ *
+ * Geometry of every entry. x [N, H, W, C]; w [KH, KW, O] with O = C M (the
+ * stored bytes of the [1, KH, KW, O] filter), M >= 1 the depth multiplier;
+ * output channel oc reads input channel oc / M. Strides, dilations, pad_top,
+ * pad_left, OH and OW are the caller's (ops.conv_geometry), and the window
+ * [first_row, first_row + row_count) over the N OH OW output rows has the
+ * gather's meaning. Outputs are row-major [row_count, O], what
+ * mi355q_sqdiff_cols_f64 reads. For t in the window and oc in [0, O):
+ *   n = t / (OH OW)      oh = (t / OW) % OH      ow = t % OW
+ *   ih = oh stride_h - pad_top + kh dil_h      iw = ow stride_w - pad_left + kw dil_w
+ * and the taps (kh, kw) are taken in ascending (kh, kw) order. A tap with ih
+ * outside [0, H) or iw outside [0, W) is SKIPPED: it adds nothing, and no
+ * element outside x is read, whatever the geometry arguments are. All index
+ * arithmetic is 64-bit.
+ *
+ * mi355q_dwconv_forward_f32 (x, w float32):
+ *   p(kh,kw) = fl32( x[n, ih, iw, oc / M] * w[kh, kw, oc] )
+ *   y_out[t - first_row, oc] = (...((0 + p_0) + p_1) + ...)      taps inside
+ * every product and every sum rounded to float32, no FMA contraction: the bits
+ * of a NumPy float32 loop in that order (a first product of -0.0 gives +0.0,
+ * as 0 + -0.0 does). This is the float op's pre-bias product, and with the
+ * dequantized filter the weight-only route. Infinities and NaNs follow IEEE.
+ *
+ * mi355q_dwconv_forward_i8 (xq int8, w int8: w_kind MI355Q_CMP_I8 alone,
+ * weight zero points 0):
+ *   acc[t,oc] = Sum_{taps inside} (xq - x_zero_point) * w          (int32, exact:
+ *               KH KW <= 65536 taps of at most 255 * 128)
+ *   y_out[t,oc] = fl32( float(acc) * fl32(x_scale[.] * w_scale[.]) )
+ * x_scale_count is 1 or N: ONE SCALE PER IMAGE, row t reads entry t / (OH OW)
+ * (the dynamic mode of the conv path); w_scale_count is 1 or O. acc_out is NULL
+ * or int32 [row_count, O].
+ *
+ * mi355q_dwconv_forward_i16 (xq int16 over its full range, no zero point):
+ *   acc exact in int64
+ *   y_out[t,oc] = fl32( double(acc) * double( fl32(x_scale[.] * w_scale[.]) ) )
+ * the rescale of mi355q_qfc_forward_i16. acc_out is NULL or int64.
+ *
+ * mi355q_dwconv_output_i8 / mi355q_dwconv_output_i16: the same accumulators
+ * taken through to the stored tensor with the arithmetic of
+ * mi355q_qfc_output_i8 / mi355q_qfc_output_i16 UNCHANGED (one piece of device
+ * code, csrc/qfc_epilogue.h): bias int32 / int64 (NULL: 0) with O entries,
+ * sat32, mbqm32 (int16: Mr, T), out_zero_point, [act_min, act_max], int8 /
+ * int16 store; multiplier and shift have mcount in {1, O} entries. The
+ * epilogue runs on the accumulator in registers and only q_out [row_count, O]
+ * is written.
+ *
+ * Routes; both give the same bits. Vector route (M == 1, C % 4 == 0, and x, w,
+ * the outputs given and the per-channel vectors given 16-byte aligned): a lane
+ * owns 4 consecutive channels of one output pixel, consecutive lanes take
+ * consecutive channel groups and then the next pixel, so that per tap the
+ * activation loads (16 / 4 / 8 bytes per lane for float32 / int8 / int16), the
+ * filter loads and the stores are contiguous across the wave; float32 y_out
+ * and int32 acc_out leave as 16-byte stores, int64 acc_out as two. The filter
+ * is read through the caches by every pixel. Generic route (every other M, C
+ * or alignment): one thread per output element. A request of 2^32 units or
+ * more runs as one launch whose lanes stride over the units with a 64-bit
+ * index. No kernel uses scratch memory.
+ *
+ * Refused before any launch, with the neighbouring entries' texts where they
+ * overlap: N, H, W, C, KH, KW, OH, OW, M, a stride or a dilation that is not
+ * positive; a negative first_row or row_count; first_row + row_count >
+ * N OH OW; a w_kind other than MI355Q_CMP_I8; x_scale_count outside {1, N},
+ * w_scale_count or mcount outside {1, O}; x_zero_point / out_zero_point
+ * outside int8; act_min > act_max or either outside the output type
+ * (MI355Q_BAD_ARG); KH KW > 65536; N OH OW > INT32_MAX; an activation beyond
+ * 2^62 bytes; O > INT32_MAX (MI355Q_UNSUPPORTED). After those row_count == 0
+ * enqueues nothing, whatever the pointers; otherwise a null x / xq, w,
+ * x_scale, w_scale, multiplier, shift, y_out or q_out is MI355Q_BAD_ARG.
+ * ------------------------------------------------------------------------ */
+int32_t mi355q_dwconv_forward_f32(const float* x, int64_t N, int64_t H, int64_t W, int64_t C, const float* w, int32_t KH,
+                                  int32_t KW, int32_t M, int32_t stride_h, int32_t stride_w, int32_t dil_h, int32_t dil_w,
+                                  int32_t pad_top, int32_t pad_left, int64_t OH, int64_t OW, int64_t first_row,
+                                  int64_t row_count, float* y_out, void* stream);
+int32_t mi355q_dwconv_forward_i8(const int8_t* xq, int64_t N, int64_t H, int64_t W, int64_t C, const float* x_scale,
+                                 int64_t x_scale_count, int32_t x_zero_point, const void* w, int32_t w_kind, int32_t KH,
+                                 int32_t KW, int32_t M, const float* w_scale, int64_t w_scale_count, int32_t stride_h,
+                                 int32_t stride_w, int32_t dil_h, int32_t dil_w, int32_t pad_top, int32_t pad_left,
+                                 int64_t OH, int64_t OW, int64_t first_row, int64_t row_count, float* y_out,
+                                 int32_t* acc_out, void* stream);
+int32_t mi355q_dwconv_forward_i16(const int16_t* xq, int64_t N, int64_t H, int64_t W, int64_t C, const float* x_scale,
+                                  int64_t x_scale_count, const void* w, int32_t w_kind, int32_t KH, int32_t KW, int32_t M,
+                                  const float* w_scale, int64_t w_scale_count, int32_t stride_h, int32_t stride_w,
+                                  int32_t dil_h, int32_t dil_w, int32_t pad_top, int32_t pad_left, int64_t OH, int64_t OW,
+                                  int64_t first_row, int64_t row_count, float* y_out, int64_t* acc_out, void* stream);
+int32_t mi355q_dwconv_output_i8(const int8_t* xq, int64_t N, int64_t H, int64_t W, int64_t C, int32_t x_zero_point,
+                                const void* w, int32_t w_kind, int32_t KH, int32_t KW, int32_t M, const int32_t* bias,
+                                const int32_t* multiplier, const int32_t* shift, int64_t mcount, int32_t out_zero_point,
+                                int32_t act_min, int32_t act_max, int32_t stride_h, int32_t stride_w, int32_t dil_h,
+                                int32_t dil_w, int32_t pad_top, int32_t pad_left, int64_t OH, int64_t OW, int64_t first_row,
+                                int64_t row_count, int8_t* q_out, void* stream);
+int32_t mi355q_dwconv_output_i16(const int16_t* xq, int64_t N, int64_t H, int64_t W, int64_t C, const void* w,
+                                 int32_t w_kind, int32_t KH, int32_t KW, int32_t M, const int64_t* bias,
+                                 const int32_t* multiplier, const int32_t* shift, int64_t mcount, int32_t act_min,
+                                 int32_t act_max, int32_t stride_h, int32_t stride_w, int32_t dil_h, int32_t dil_w,
+                                 int32_t pad_top, int32_t pad_left, int64_t OH, int64_t OW, int64_t first_row,
+                                 int64_t row_count, int16_t* q_out, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
