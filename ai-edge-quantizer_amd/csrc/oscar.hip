@@ -4,7 +4,8 @@
 // The O(in_ch) vector algebra (geometric-mean normalisation, log/exp, clamps) stays on the host in
 // NumPy exactly as the reference does it; everything that touches the [out_ch, in_ch] matrix is
 // here:
-//   col_sumsq      per-column sum of squares, rows added in order (NumPy's axis-0 order)
+//   col_sumsq      per-column sum of squares, rows added in order (NumPy's axis-0 order; a single
+//                  column is summed as NumPy sums a vector)
 //   group_terms    per (row, group) max of |w|*s with first-index argmax, then per group the
 //                  NumPy-order (8192-chunk, pairwise) sum over rows of the squared maxima
 //   winner_energy  the np.add.at accumulation of the winners' squares, per column, rows in order
@@ -172,7 +173,9 @@ __device__ double pairwise_f64(const double* a, int64_t n) {
   return pairwise_f64(a, n2) + pairwise_f64(a + n2, n - n2);
 }
 
-// Leaves of pairwise_f64's recursion over [lo, lo + n), in order.
+// Leaves of pairwise_f64's recursion over [lo, lo + n), in order. (Templates on the caller's element type: these two
+// are real calls, and a copy per kernel keeps each kernel's register budget its own.)
+template <typename T>
 __device__ void pairwise_leaves(int32_t lo, int32_t n, int32_t* leaf_lo, int32_t* leaf_n,
                                 int32_t* count) {
   if (n <= 128) {
@@ -183,17 +186,18 @@ __device__ void pairwise_leaves(int32_t lo, int32_t n, int32_t* leaf_lo, int32_t
   }
   int32_t n2 = n / 2;
   n2 -= n2 % 8;
-  pairwise_leaves(lo, n2, leaf_lo, leaf_n, count);
-  pairwise_leaves(lo + n2, n - n2, leaf_lo, leaf_n, count);
+  pairwise_leaves<T>(lo, n2, leaf_lo, leaf_n, count);
+  pairwise_leaves<T>(lo + n2, n - n2, leaf_lo, leaf_n, count);
 }
 
 // The recursion again, with the leaves' sums already known (consumed in order).
+template <typename T>
 __device__ double pairwise_combine(int32_t n, const double* leaf_sum, int32_t* next) {
   if (n <= 128) return leaf_sum[(*next)++];
   int32_t n2 = n / 2;
   n2 -= n2 % 8;
-  const double left = pairwise_combine(n2, leaf_sum, next);
-  return left + pairwise_combine(n - n2, leaf_sum, next);
+  const double left = pairwise_combine<T>(n2, leaf_sum, next);
+  return left + pairwise_combine<T>(n - n2, leaf_sum, next);
 }
 
 // np.sum of a contiguous FP64 vector: 8192-element chunks added in order, each pairwise. One
@@ -201,33 +205,42 @@ __device__ double pairwise_combine(int32_t n, const double* leaf_sum, int32_t* n
 // accumulator of NumPy's unrolled loop (so a wave reads 8 x 64 B runs per step), the
 // accumulators are folded pairwise by an xor butterfly, which is the ((r0+r1)+(r2+r3))+... tree;
 // lane 0 folds the leaf sums in the recursion's order.
-__global__ __launch_bounds__(64) void group_sum_kernel(const double* __restrict__ top2, int64_t n,
-                                                       double* __restrict__ sums) {
+// T = float: the terms are the FP64 squares of float32 values and the sum is divided by mean_rows when that is not 0
+// (col_sumsq of a single column, which NumPy adds as the contiguous vector it is, not row by row).
+__device__ __forceinline__ double sum_term(const double* p, int64_t i) { return p[i]; }
+__device__ __forceinline__ double sum_term(const float* p, int64_t i) {
+  const double t = static_cast<double>(p[i]);
+  return t * t;
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void group_sum_kernel(const T* __restrict__ top2, int64_t n,
+                                                       double* __restrict__ sums, int64_t mean_rows) {
   __shared__ int32_t leaf_lo[128], leaf_n[128], leaves;
   __shared__ double leaf_sum[128];
-  const double* a = top2 + static_cast<int64_t>(blockIdx.x) * n;
+  const T* a = top2 + static_cast<int64_t>(blockIdx.x) * n;
   const int lane = threadIdx.x, k = lane & 7, slot = lane >> 3;
   double total = 0.0;
   for (int64_t lo = 0; lo < n; lo += 8192) {
     const int32_t len = static_cast<int32_t>((n - lo < 8192) ? n - lo : 8192);
     if (lane == 0) {
       int32_t c = 0;
-      pairwise_leaves(0, len, leaf_lo, leaf_n, &c);
+      pairwise_leaves<T>(0, len, leaf_lo, leaf_n, &c);
       leaves = c;
     }
     __syncthreads();
     for (int32_t base = 0; base < leaves; base += 8) {
       const int32_t leaf = base + slot;
       const bool live = leaf < leaves;
-      const double* p = a + lo + (live ? leaf_lo[leaf] : 0);
+      const T* p = a + lo + (live ? leaf_lo[leaf] : 0);
       const int32_t ln = live ? leaf_n[leaf] : 0;
       double res = 0.0;
       if (ln < 8) {                                  // short leaf: plain left-to-right sum
-        for (int32_t i = 0; i < ln; ++i) res = res + p[i];
+        for (int32_t i = 0; i < ln; ++i) res = res + sum_term(p, i);
       } else {
         double v[16];                                // all loads first, then the ordered adds
 #pragma unroll
-        for (int u = 0; u < 16; ++u) v[u] = (8 * (u + 1) <= ln) ? p[8 * u + k] : 0.0;
+        for (int u = 0; u < 16; ++u) v[u] = (8 * (u + 1) <= ln) ? sum_term(p, 8 * u + k) : 0.0;
         double r = v[0];
 #pragma unroll
         for (int u = 1; u < 16; ++u)
@@ -236,7 +249,7 @@ __global__ __launch_bounds__(64) void group_sum_kernel(const double* __restrict_
         r = r + __shfl_xor(r, 1, kWave);             // IEEE addition commutes: both partners agree
         r = r + __shfl_xor(r, 2, kWave);
         r = r + __shfl_xor(r, 4, kWave);
-        for (; i < ln; ++i) r = r + p[i];
+        for (; i < ln; ++i) r = r + sum_term(p, i);
         res = r;
       }
       if (live && k == 0) leaf_sum[leaf] = res;
@@ -244,12 +257,16 @@ __global__ __launch_bounds__(64) void group_sum_kernel(const double* __restrict_
     __syncthreads();
     if (lane == 0) {
       int32_t next = 0;
-      const double part = pairwise_combine(len, leaf_sum, &next);
+      const double part = pairwise_combine<T>(len, leaf_sum, &next);
       total = (lo == 0) ? part : total + part;
     }
     __syncthreads();
   }
-  if (lane == 0) sums[blockIdx.x] = total;
+  if constexpr (sizeof(T) == sizeof(float)) {
+    if (lane == 0) sums[blockIdx.x] = mean_rows ? total / static_cast<double>(mean_rows) : total;
+  } else {
+    if (lane == 0) sums[blockIdx.x] = total;
+  }
 }
 
 // The same sum when every chunk's tree is complete (balanced_chunk, common.h; n = 2048, 4096,
@@ -1265,6 +1282,12 @@ extern "C" int32_t mi355q_oscar_col_sumsq_f32(const float* x, int64_t rows, int6
   if (!x || !out) return fail(MI355Q_BAD_ARG, "oscar_col_sumsq: null pointer");
   if (rows <= 0 || d <= 0) return fail(MI355Q_BAD_SHAPE, "oscar_col_sumsq: rows=%lld d=%lld",
                                        (long long)rows, (long long)d);
+  if (d == 1) {   // a contiguous vector to NumPy: the 8192-chunk pairwise sum, not rows in order
+    hipLaunchKernelGGL(group_sum_kernel<float>, dim3(1), dim3(64), 0, as_stream(stream), x, rows, out,
+                       mean ? rows : static_cast<int64_t>(0));
+    MI355Q_CHECK_LAUNCH("oscar_col_sumsq");
+    return MI355Q_OK;
+  }
   const unsigned blocks = static_cast<unsigned>((d + 63) / 64);
   hipLaunchKernelGGL(col_sumsq_kernel<64>, dim3(blocks), dim3(64), 0, as_stream(stream), x, rows, d,
                      mean, out);
@@ -1309,8 +1332,8 @@ extern "C" int32_t mi355q_oscar_group_terms_f32(const float* w, const double* s,
     hipLaunchKernelGGL(group_sum_balanced_kernel, dim3(static_cast<unsigned>(G)), dim3(64), 0, st,
                        top2_workspace, n, leaf, depth, sums_out);
   else
-    hipLaunchKernelGGL(group_sum_kernel, dim3(static_cast<unsigned>(G)), dim3(64), 0, st,
-                       top2_workspace, n, sums_out);
+    hipLaunchKernelGGL(group_sum_kernel<double>, dim3(static_cast<unsigned>(G)), dim3(64), 0, st,
+                       top2_workspace, n, sums_out, static_cast<int64_t>(0));
   MI355Q_CHECK_LAUNCH("oscar_group_sum");
   return MI355Q_OK;
 }

@@ -552,7 +552,8 @@ int32_t mi355q_gptq_apply_wide_f32(const float* w, int64_t rows, int64_t d, cons
  * (geometric-mean normalisation, clamps) is host NumPy, as in the reference.
  * ref: algorithms/uniform_quantize/oscar.py
  * ------------------------------------------------------------------------ */
-/* out[j] = sum_r x[r, j]^2 (rows added in order), divided by rows when mean != 0.
+/* out[j] = sum_r x[r, j]^2 (rows added in order), divided by rows when mean != 0. A single column (d == 1) is a
+ * contiguous vector to NumPy, which adds it as np.sum does: 8192-element chunks in order, each pairwise.
  *   mean=1: calibration statistic mu2 = np.mean(x*x, axis=0)            (ref oscar.py:318-324)
  *   mean=0: column energies (w*w).sum(0)                                 (ref oscar.py:224) */
 int32_t mi355q_oscar_col_sumsq_f32(const float* x, int64_t rows, int64_t d, int32_t mean,
@@ -562,7 +563,9 @@ int32_t mi355q_oscar_col_sumsq_f32(const float* x, int64_t rows, int64_t d, int3
  *   sums_out[k] = np.sum over rows of top^2 for group k (8192-chunk pairwise order).
  * The objective of ref oscar.py:175-194 is sum_k sums_out[k] * mass_k (host); winner / wsq
  * feed mi355q_oscar_winner_energy_f64 (ref oscar.py:236-246).
- *   top2_workspace double [d/g * n]; winner_out int32 [d/g, n]; wsq_out double [d/g, n] */
+ *   top2_workspace double [d/g * n]; winner_out int32 [d/g, n]; wsq_out double [d/g, n]
+ * The blockwise route (g != d) reads w as float4 and s as double2: w and s must be 16-byte aligned, and d is a
+ * multiple of g, hence of 4, so that every row of w starts on such a boundary. */
 int32_t mi355q_oscar_group_terms_f32(const float* w, const double* s, int64_t n, int64_t d,
                                      int32_t g, double* top2_workspace, int32_t* winner_out,
                                      double* wsq_out, double* sums_out, void* stream);
