@@ -275,7 +275,7 @@ int32_t mi355q_hist_bins_f32(const float* const* x_ptrs, const int64_t* outer,
  *   workspace : mi355q_octav_workspace_bytes(units, max_iter) bytes
  * ------------------------------------------------------------------------ */
 size_t mi355q_octav_workspace_bytes(int64_t units, int32_t max_iter);
-/* The same plus, for units of 1024 .. 16384 elements (weight rows), room for the hand-over of a
+/* The same plus, for units of 129 .. 16384 elements (the rows kernel's: weight rows), room for the hand-over of a
  * row's late iterations to a one-wave tail kernel (the few per cent of a row a converging guess still
  * selects are listed once and re-tested instead of the row): a caller that passes this much gets
  * that path, one that passes mi355q_octav_workspace_bytes() gets every iteration from the row's own

@@ -392,9 +392,13 @@ def test_octav_masked_sums_with_designed_run_lengths(m, seed):
 
 @pytest.mark.parametrize("block", [32, 64, 128, 256, 512])
 def test_octav_blockwise_groups_kernel_bit_exact(m, block):
-  """Blockwise units of 32 .. 512 elements go through octav_groups_kernel (4096 contiguous elements =
-  8 .. 128 whole units per workgroup, csrc/reduce_exact.hip) when the tensor is a whole number of
-  groups. Designed content: runs of selected elements of every length up to the block size, ending
+  """Blockwise units on a tensor that is a whole number of 4096-element groups. By the dispatch of
+  mi355q_octav_clip_f32 (csrc/reduce_exact.hip) blocks of 32 / 64 / 128 / 256 take the lane-per-unit
+  kernel here (octav_groups_kernel -- 4096 contiguous elements = 32 .. 128 whole units per workgroup --
+  only with MI355Q_OCTAV_UNIT_LANES=0, and then not for 256), and blocks of 256 without that kernel
+  and of 512 take the rows kernel, as every unit of 129 .. 16384 elements does (the name is from
+  before; the groups kernel itself is compared in test_gpu_octav_unit_lanes.py and
+  test_gpu_octav_routes.py). Designed content: runs of selected elements of every length up to the block size, ending
   at / crossing piece (16) and block boundaries -- where a run must stop --, all-selected blocks
   (runs longer than 128 in blocks of 256 / 512), all-small blocks, single outliers at a block's
   first and last element, NaN / inf, and plain weight-like data; blocks differ, so their guesses
