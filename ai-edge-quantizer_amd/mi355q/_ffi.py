@@ -160,6 +160,12 @@ PROTOTYPES = {
     "mi355q_dwconv_output_i16": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_i32, c_ptr, c_ptr,
                                          c_ptr, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i64, c_i64,
                                          c_i64, c_i64, c_ptr, c_ptr]),
+    "mi355q_qbmm_mfma_route": (c_i64, [c_ptr, c_i64, c_i64, c_i32, c_ptr, c_i64, c_i32]),
+    "mi355q_qbmm_workspace_bytes": (c_size, [c_i64, c_i64, c_i64, c_i32, c_i64, c_i64, c_i32]),
+    "mi355q_qbmm_forward_i8": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_ptr, c_i64, c_i32, c_ptr, c_i64, c_i64, c_i32,
+                                       c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "mi355q_qbmm_output_i8": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i32, c_i32, c_ptr, c_i64, c_i64, c_i32, c_i32, c_ptr,
+                                      c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_sqdiff_cols_workspace_bytes": (c_size, [c_i64, c_i64]),
     "mi355q_sqdiff_cols_f64": (c_i32, [c_ptr, c_ptr, c_i64, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_size, c_ptr]),
     "mi355q_clock_probe": (c_i32, [c_f64, c_ptr, c_ptr]),

@@ -963,6 +963,63 @@ def _depthwise_conv_2d_ops(m, sg_index: int):
   return out
 
 
+# `batch_matmul`: BATCH_MATMUL ops, executed by the integer batched product (csrc/qbmm.hip)
+_BATCH_MATMUL = 126
+SKIP_BMM_RANK = "an operand has rank below 2, or the two operands disagree about K"
+SKIP_BMM_BATCH = ("the batch dimensions are neither equal nor a right-hand batch product of 1 (general broadcasting is"
+                  " not built)")
+SKIP_BMM_KIND = "the target constant is not int8"
+SKIP_BMM_BLOCKWISE = "the constant has blockwise scales"
+SKIP_BMM_SCALE_AXIS = "the constant's per-channel scales are not along its output axis"
+SKIP_BMM_DYNAMIC_ADJ_X = "a dynamic-range op with adjX: the per-row scales would lie along K"
+SKIP_BMM_MISMATCH = "the float op and the target op disagree about adjX or adjY, or one carries another op's options"
+SKIP_BMM_K = "K exceeds 32768 (the int32 accumulator)"
+SKIP_BMM_FLOAT = "the target op is a float op (not quantized)"
+OPERANDS_CONSTANT, OPERANDS_ACTIVATIONS = "constant", "activations"
+
+
+def batch_matmul_options(op) -> Optional[dict]:
+  """BatchMatMulOptions of a BATCH_MATMUL op as {adj_x, adj_y, asymmetric_quantize_inputs} (booleans; the schema's
+  defaults, False, for absent fields and for an op without options). None when the op carries the options of another
+  op type."""
+  o = op.builtinOptions
+  if o is None:
+    return {"adj_x": False, "adj_y": False, "asymmetric_quantize_inputs": False}
+  if not hasattr(o, "adjX") or not hasattr(o, "adjY"):
+    return None
+  return {"adj_x": bool(o.adjX), "adj_y": bool(o.adjY),
+          "asymmetric_quantize_inputs": bool(getattr(o, "asymmetricQuantizeInputs", False))}
+
+
+def _batch_matmul_ops(m, sg_index: int):
+  """(op, lhs tensor, rhs tensor, output name) of every BATCH_MATMUL op of a subgraph."""
+  sg = m.subgraphs[sg_index]
+  out = []
+  for op in sg.operators or []:
+    if (int(m.operatorCodes[op.opcodeIndex].builtinCode) != _BATCH_MATMUL or len(op.inputs) < 2 or op.inputs[0] < 0
+        or op.inputs[1] < 0):
+      continue
+    out.append((op, sg.tensors[op.inputs[0]], sg.tensors[op.inputs[1]], schema.tensor_name(sg.tensors[op.outputs[0]])))
+  return out
+
+
+def _bmm_geometry(a_shape, b_shape, adj_x: bool, adj_y: bool):
+  """(batch, b_batch, M, K, N) of two operand shapes, or the SKIP_BMM_* reason they have none."""
+  a_shape, b_shape = [int(v) for v in a_shape], [int(v) for v in b_shape]
+  if len(a_shape) < 2 or len(b_shape) < 2:
+    return SKIP_BMM_RANK
+  k, m = (a_shape[-2], a_shape[-1]) if adj_x else (a_shape[-1], a_shape[-2])
+  n, kb = (b_shape[-2], b_shape[-1]) if adj_y else (b_shape[-1], b_shape[-2])
+  if k != kb:
+    return SKIP_BMM_RANK
+  batch, b_batch = int(np.prod(a_shape[:-2], dtype=np.int64)), int(np.prod(b_shape[:-2], dtype=np.int64))
+  if a_shape[:-2] != b_shape[:-2] and b_batch != 1:
+    return SKIP_BMM_BATCH
+  if k > 32768:
+    return SKIP_BMM_K
+  return batch, (batch if a_shape[:-2] == b_shape[:-2] else 1), m, k, n
+
+
 def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray,
                  option=_fc_option):
   """An OutputPlan, or the FINAL_SKIP_* reason there is none. `option(op, field)` reads an op's options
@@ -1113,6 +1170,36 @@ class LayerExecutionKernels:
     return ops.dwconv_output_i16(xq, target, kernel[0], kernel[1], strides, dilations, padding, bias, multiplier, shift,
                                  act_min, act_max, depth_multiplier, first, count)
 
+  # (`batch_matmul`: operands of rank 3, [batch, ., .], the right-hand one with a batch of 1 or the left's)
+  def sample_nd(self, value):
+    """A sample entry of any rank (array or device tensor) as a contiguous float32 tensor of its own shape."""
+    import torch
+    from . import runtime as rt
+    return rt.on_device(rt.resident_sample(value), torch.float32).contiguous()
+
+  def bmm_constant(self, plan: ConstantPlan, shape: tuple):
+    """(int8 [b_batch, ., .], float32 scales): the stored integers and the scales of an int8 constant."""
+    from . import runtime as rt
+    return rt.to_device(np.ascontiguousarray(plan.data, np.int8)).view(shape), rt.to_device(np.asarray(plan.scale, np.float32))
+
+  def bmm_float(self, a, b, adj_x: bool, adj_y: bool):
+    """float32 [M, N] = op(a) op(b) of one batch slice (ops.gemm)."""
+    from . import ops
+    return ops.gemm(a, b, trans_a=adj_x, trans_b=adj_y)
+
+  def bmm_forward(self, aq, bq, adj_x: bool, adj_y: bool, a_scale, a_zero_point: int, b_scale, b_zero_point: int):
+    """float32 [batch, M, N] of two int8 operands with a zero point each (ops.qbmm_forward)."""
+    from . import ops
+    return ops.qbmm_forward(aq, bq, adj_x=adj_x, adj_y=adj_y, a_scale=a_scale, a_zero_point=a_zero_point, b_scale=b_scale,
+                            b_zero_point=b_zero_point)
+
+  def bmm_output(self, aq, bq, adj_x: bool, adj_y: bool, a_zero_point: int, b_zero_point: int, multiplier, shift,
+                 out_zero_point: int):
+    """int8 [batch, M, N]: what the static op stores (ops.qbmm_output)."""
+    from . import ops
+    return ops.qbmm_output(aq, bq, adj_x=adj_x, adj_y=adj_y, a_zero_point=a_zero_point, b_zero_point=b_zero_point,
+                           multiplier=multiplier, shift=shift, out_zero_point=out_zero_point)
+
   def transform(self, x, kind: str, multiplier, hadamard_size: int):
     """The inserted op's own map on rows of length d: x * multiplier, or x R with R = blockdiag(H_h / sqrt(h))."""
     from . import ops
@@ -1243,7 +1330,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                             int16_activations: bool = False,
                             quantized_outputs: bool = False,
                             conv_2d: bool = False,
-                            depthwise_conv_2d: bool = False) -> LayerExecutionComparison:
+                            depthwise_conv_2d: bool = False,
+                            batch_matmul: bool = False) -> LayerExecutionComparison:
   """Executes every quantized FULLY_CONNECTED op in integers on the calibration samples and compares it with the
   float model's product, for every op of the float model with a constant 2-D float32 weight [rows, d] whose input 0
   is in `samples` (the {tensor name: array or device tensor} maps calibrate() takes; tensors of any rank are rows of
@@ -1332,7 +1420,27 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
   that is not O / C), SKIP_DEPTHWISE_KIND, SKIP_DEPTHWISE_BLOCKWISE, SKIP_DEPTHWISE_SCALE_AXIS,
   SKIP_DEPTHWISE_MISMATCH (the two ops' options differ); the reasons of CONV_2D that apply keep their texts.
   Without the keyword nothing changes.
-  """
+
+  With `batch_matmul` every BATCH_MATMUL op of the float model whose inputs are sampled is executed as well, by the
+  integer batched product (ops.qbmm_forward, csrc/qbmm.hip); the target op is the producer of the same-named output,
+  BatchMatMulOptions are read by batch_matmul_options and must agree. `operands` = "constant" (the float model's rhs is
+  a constant float32 of rank >= 2): "static" (lhs INT8 with one scale and zero point, the int8 constant with scales per
+  tensor or along its output axis, common_utils.get_bmm_weight_quantized_dim), "dynamic" (lhs FLOAT32, rows of
+  [batch M, K] quantized by ops.qfc_quantize_rows; not with adjX) or "weight_only" (the constant behind a DEQUANTIZE:
+  Yq is the float product with the dequantized constant). `operands` = "activations" (both inputs sampled): "static",
+  both INT8 with one scale and a zero point of its own each, each the float input itself or a QUANTIZE of it: the place
+  where two rounded activations multiply. Y is the float32 product of the float model's own operands (ops.gemm per
+  batch slice), the errors go through ops.sqdiff_cols on [batch M, N] rows in chunks. An entry carries `op` =
+  "BATCH_MATMUL", `operands`, `adj_x`, `adj_y`, `batch` (of the first sample), `rows` = N, `d` = K, `tokens` = Sum
+  batch M, `mode`, `activation_bits`, and with `quantized_outputs` and an INT8 output with one scale `final_*` from
+  ops.qbmm_output with ops.quantize_multiplier(s_a s_b[n] / s_y) (the op has neither bias nor fused activation), else
+  `final_skipped`. Skipped with a SKIP_BMM_* reason: operands of rank < 2 or disagreeing about K; batch dimensions that
+  are neither equal nor a right-hand product of 1; a constant that is not int8, has blockwise scales or scales off
+  the output axis; a dynamic op with adjX; differing options; K > 32768; a float target op. INT16 inputs are
+  SKIP_INT16, a constant with a zero point SKIP_WEIGHT_ZERO_POINT. The arithmetic is this library's own definition,
+  modelled on LiteRT's BATCH_MATMUL; agreement with LiteRT's kernels is unchecked. Every entry carries `op` whenever
+  this or a conv keyword is on.
+"""
   kernels = kernels or LayerExecutionKernels()
   samples = list(samples)
   ref, tgt = _as_model(reference_model), _as_model(target_model)
@@ -1500,9 +1608,9 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                      final_per_channel_error=f_channel)
       elif final is not None:
         entry["final_skipped"] = final
-    if conv_2d or depthwise_conv_2d:
+    if conv_2d or depthwise_conv_2d or batch_matmul:
       out.results[y_name]["op"] = "FULLY_CONNECTED"
-  if not (conv_2d or depthwise_conv_2d):
+  if not (conv_2d or depthwise_conv_2d or batch_matmul):
     return out
 
   # ---- CONV_2D: the same product on patch rows (the docstring's section on `conv_2d`)
@@ -1688,11 +1796,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                      final_per_channel_error=f_channel)
       elif final is not None:
         entry["final_skipped"] = final
-  if not depthwise_conv_2d:
-    return out
-
   # ---- DEPTHWISE_CONV_2D: a direct convolution, no patch rows (the docstring's section on `depthwise_conv_2d`)
-  for ref_op, x_name, w, y_name in _depthwise_conv_2d_ops(ref, sg_ref):
+  for ref_op, x_name, w, y_name in (_depthwise_conv_2d_ops(ref, sg_ref) if depthwise_conv_2d else []):
     w_name = schema.tensor_name(w)
     if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
         or int(w.shape[0]) != 1 or min(int(v) for v in w.shape) < 1):
@@ -1876,7 +1981,223 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                      final_per_channel_error=f_channel)
       elif final is not None:
         entry["final_skipped"] = final
+  if batch_matmul:
+    _batch_matmul_entries(out, ref, sg_ref, tgt, tgt_sg, producers, producer_op, samples, kernels, quantized_outputs,
+                          follow_input_transforms, int16_activations)
   return out
+
+
+def _batch_matmul_entries(out, ref, sg_ref, tgt, tgt_sg, producers, producer_op, samples, kernels, quantized_outputs,
+                          follow_input_transforms, int16_activations) -> None:
+  """The BATCH_MATMUL entries of compare_layer_execution (its docstring's section on `batch_matmul`)."""
+  from . import ops
+  from .algorithms.utils import common_utils
+
+  def code(op) -> int:
+    return int(tgt.operatorCodes[op.opcodeIndex].builtinCode)
+
+  def name(index) -> Optional[str]:
+    return schema.tensor_name(tgt_sg.tensors[index]) if index is not None and index >= 0 else None
+
+  def int8_input(index, want_name):
+    """(scale, zero point) of the target op's INT8 input `index` that is `want_name` itself or a QUANTIZE of it; a
+    SKIP_* reason otherwise."""
+    t = tgt_sg.tensors[index]
+    if t.type == schema.TensorType.INT16:
+      return SKIP_INT16
+    if t.type != schema.TensorType.INT8:
+      return SKIP_INPUT
+    q = t.quantization
+    source = name(index)
+    quantize = producers.get(int(index))
+    if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
+      source = name(quantize.inputs[0])
+    if q is None or q.scale is None or len(q.scale) != 1 or source != want_name:
+      return SKIP_INPUT
+    zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
+    if not -128 <= zero_point <= 127:
+      return SKIP_INPUT
+    return float(np.float32(q.scale[0])), zero_point
+
+  float_types = (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16)
+  for ref_op, lhs, rhs, y_name in _batch_matmul_ops(ref, sg_ref):
+    a_name, b_name = schema.tensor_name(lhs), schema.tensor_name(rhs)
+    constant = _has_data(ref.buffers, rhs)
+    if constant and (rhs.type != schema.TensorType.FLOAT32 or rhs.shape is None or len(rhs.shape) < 2):
+      out.skipped[y_name] = SKIP_BMM_RANK
+      continue
+    operands = OPERANDS_CONSTANT if constant else OPERANDS_ACTIVATIONS
+    bmm = producer_op.get(y_name)
+    if bmm is None or code(bmm) != _BATCH_MATMUL or len(bmm.inputs) < 2 or bmm.inputs[0] < 0 or bmm.inputs[1] < 0:
+      out.skipped[y_name] = SKIP_TARGET
+      continue
+    options, float_options = batch_matmul_options(bmm), batch_matmul_options(ref_op)
+    if (options is None or float_options is None
+        or any(options[k] != float_options[k] for k in ("adj_x", "adj_y"))):
+      out.skipped[y_name] = SKIP_BMM_MISMATCH
+      continue
+    adj_x, adj_y = options["adj_x"], options["adj_y"]
+    a_in = tgt_sg.tensors[bmm.inputs[0]]
+    plan, b_quant, a_quant, through_dequantize = None, None, None, False
+    if constant:
+      # ---- the constant the target op reads: the integer constant itself, or a DEQUANTIZE of it
+      read = tgt_sg.tensors[bmm.inputs[1]]
+      target = read
+      if not _has_data(tgt.buffers, read):
+        deq = producers.get(int(bmm.inputs[1]))
+        if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
+          out.skipped[y_name] = SKIP_TARGET
+          continue
+        target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
+      if schema.tensor_name(target) != b_name or not _has_data(tgt.buffers, target) or _numel(target) != _numel(rhs):
+        out.skipped[y_name] = SKIP_TARGET
+        continue
+      if target.type in float_types:
+        out.skipped[y_name] = SKIP_BMM_FLOAT
+        continue
+      if a_in.type == schema.TensorType.FLOAT32 and name(bmm.inputs[0]) == a_name:
+        mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
+      else:
+        a_quant = SKIP_INPUT if through_dequantize else int8_input(bmm.inputs[0], a_name)
+        if isinstance(a_quant, str):
+          out.skipped[y_name] = a_quant
+          continue
+        mode = MODE_STATIC
+      values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(rhs, ref.buffers), np.float32))
+      plan = _target_plan(b_name, values, tgt, target)
+      if plan is None or not plan.dequantized:
+        out.skipped[y_name] = SKIP_TARGET
+        continue
+      if plan.kind != "i8":
+        out.skipped[y_name] = SKIP_BMM_KIND
+        continue
+      if plan.scale is None:
+        out.skipped[y_name] = SKIP_BMM_BLOCKWISE
+        continue
+      b_shape = [int(v) for v in rhs.shape]
+      axis = common_utils.get_bmm_weight_quantized_dim(np.empty(b_shape, np.int8), adj_y)
+      inner = int(np.prod(b_shape[axis + 1:])) if axis + 1 < len(b_shape) else 1
+      if (not (plan.channels == 1 or (plan.channels == b_shape[axis] and plan.inner == inner))
+          or np.asarray(plan.scale).size != plan.channels):
+        out.skipped[y_name] = SKIP_BMM_SCALE_AXIS
+        continue
+      if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
+        out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
+        continue
+      if mode == MODE_DYNAMIC and adj_x:
+        out.skipped[y_name] = SKIP_BMM_DYNAMIC_ADJ_X
+        continue
+    else:
+      b_in = tgt_sg.tensors[bmm.inputs[1]]
+      if a_in.type in float_types and b_in.type in float_types:
+        out.skipped[y_name] = SKIP_BMM_FLOAT
+        continue
+      a_quant, b_quant = int8_input(bmm.inputs[0], a_name), int8_input(bmm.inputs[1], b_name)
+      bad = a_quant if isinstance(a_quant, str) else b_quant if isinstance(b_quant, str) else None
+      if bad is not None:
+        out.skipped[y_name] = bad
+        continue
+      mode = MODE_STATIC
+    # ---- the samples and their geometry
+    present = [s for s in samples if a_name in s and (constant or b_name in s)]
+    if not present:
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    geometries = [_bmm_geometry(s[a_name].shape, rhs.shape if constant else s[b_name].shape, adj_x, adj_y) for s in present]
+    bad = next((g for g in geometries if isinstance(g, str)), None)
+    if bad is not None:
+      out.skipped[y_name] = bad
+      continue
+    d, rows = geometries[0][3], geometries[0][4]
+    if any(g[3] != d or g[4] != rows for g in geometries):
+      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
+      continue
+    # ---- the output grid (static ops, `quantized_outputs`)
+    final, final_sums = None, None
+    s_b = np.asarray(plan.scale, np.float32).reshape(-1) if constant else np.array([b_quant[0]], np.float32)
+    if quantized_outputs and mode == MODE_STATIC:
+      y_t = tgt_sg.tensors[bmm.outputs[0]]
+      q = y_t.quantization
+      zp_y = int(q.zeroPoint[0]) if q is not None and q.zeroPoint is not None and len(q.zeroPoint) else 0
+      s_y = float(np.float32(q.scale[0])) if q is not None and q.scale is not None and len(q.scale) == 1 else 0.0
+      if y_t.type != schema.TensorType.INT8 or not (np.isfinite(s_y) and s_y > 0) or not -128 <= zp_y <= 127:
+        final = FINAL_SKIP_OUTPUT
+      else:
+        lo, hi = ops.QFC_SHIFT_RANGE[8]
+        try:
+          tables = [ops.quantize_multiplier(float(np.float32(a_quant[0])) * float(s) / s_y) for s in s_b.tolist()]
+          final = FINAL_SKIP_MULTIPLIER if any(not lo <= e <= hi for _, e in tables) else (
+              [m for m, _ in tables], [e for _, e in tables], s_y, zp_y)
+        except ValueError:
+          final = FINAL_SKIP_MULTIPLIER
+    if constant:
+      b_shape3 = (int(np.prod(b_shape[:-2], dtype=np.int64)), b_shape[-2], b_shape[-1])
+      b_float = kernels.weight(values, b_shape3[0] * b_shape3[1], b_shape3[2]).reshape(b_shape3)
+      t_dev = kernels.target(plan)
+      if mode == MODE_WEIGHT_ONLY:
+        b_deq = kernels.dequantized(t_dev, b_shape3[0] * b_shape3[1], b_shape3[2]).reshape(b_shape3)
+      else:
+        bq, b_scale = kernels.bmm_constant(plan, b_shape3)
+    sums, tokens = None, 0
+    for s, (batch, b_batch, m, _, _) in zip(present, geometries):
+      if batch * m == 0:
+        continue
+      a = kernels.sample_nd(s[a_name])
+      a3 = a.reshape((batch,) + tuple(a.shape[-2:]))
+      if not constant:
+        b_act = kernels.sample_nd(s[b_name])
+        b_float = b_act.reshape((b_batch,) + tuple(b_act.shape[-2:]))
+      # the sample is quantized ONCE, as the op sees it
+      if mode == MODE_STATIC:
+        aq, a_scale = kernels.quantize_static(a3, *a_quant)
+        if not constant:
+          bq, b_scale = kernels.quantize_static(b_float, *b_quant)
+        zps = (a_quant[1], 0 if constant else b_quant[1])
+        yq = kernels.bmm_forward(aq, bq, adj_x, adj_y, a_scale, zps[0], b_scale, zps[1])
+        if isinstance(final, tuple):
+          q_out = kernels.bmm_output(aq, bq, adj_x, adj_y, zps[0], zps[1], final[0], final[1], final[3])
+          y_final = kernels.dequantize_output(q_out, final[2], final[3])
+      elif mode == MODE_DYNAMIC:
+        aq, a_scale = kernels.quantize_dynamic(a3.reshape(batch * m, d))
+        yq = kernels.bmm_forward(aq.reshape(batch, m, d), bq, adj_x, adj_y, a_scale, 0, b_scale, 0)
+      for i in range(batch):
+        j = i if b_batch != 1 else 0
+        y = kernels.bmm_float(a3[i], b_float[j], adj_x, adj_y)
+        yq_i = kernels.bmm_float(a3[i], b_deq[j], adj_x, adj_y) if mode == MODE_WEIGHT_ONLY else yq[i]
+        for first in range(0, m, EXECUTION_CHUNK_ROWS):
+          count = min(EXECUTION_CHUNK_ROWS, m - first)
+          y_c = kernels.rows(y, first, count)
+          sums = kernels.sqdiff(kernels.rows(yq_i, first, count), y_c, sums)
+          if isinstance(final, tuple):
+            final_sums = kernels.sqdiff(kernels.rows(y_final[i], first, count), y_c, final_sums)
+      tokens += batch * m
+    if sums is None:          # (every sample was empty)
+      out.skipped[y_name] = SKIP_NO_SAMPLE
+      continue
+    sq_diff, sq_ref = kernels.host(sums)
+    per_channel = np.asarray(sq_diff, np.float64) / tokens
+    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
+    mse = error / rows
+    entry = out.results[y_name] = {
+        "op": "BATCH_MATMUL", "operands": operands, "adj_x": adj_x, "adj_y": adj_y, "batch": geometries[0][0],
+        "weight": b_name if constant else None, "input": a_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
+        "signal": signal, "error": error, "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
+        "per_channel_error": per_channel, "activation_bits": 8 if mode == MODE_STATIC else None}
+    if not constant:
+      entry["input_b"] = b_name
+    if follow_input_transforms:
+      entry.update(input_transform=TRANSFORM_NONE, hadamard_size=0)
+    if quantized_outputs:
+      entry["output_bits"] = 8 if mode == MODE_STATIC else None
+      if isinstance(final, tuple):
+        f_diff, f_ref = kernels.host(final_sums)
+        f_channel = np.asarray(f_diff, np.float64) / tokens
+        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
+        f_mse = f_error / rows
+        entry.update(fused_activation="NONE", final_signal=f_signal, final_error=f_error, final_output_mse=f_mse,
+                     final_output_snr=(f_signal / rows) / (f_mse + 1e-9), final_per_channel_error=f_channel)
+      elif final is not None:
+        entry["final_skipped"] = final
 
 
 # ----------------------------------------------------------------------------- sensitivity sweep

@@ -1551,6 +1551,95 @@ def dwconv_output_i16(x: torch.Tensor, target: CompareTarget, kh: int, kw: int, 
   return q
 
 
+QBMM_MAX_K = 32768      # K * 255 * 255 < 2^31 (include/mi355q.h, "Integer batched matrix product")
+
+
+def _qbmm_shapes(who: str, a: torch.Tensor, b: torch.Tensor, adj_x: bool, adj_y: bool, a_zero_point: int,
+                 b_zero_point: int) -> tuple:
+  """The checks qbmm_forward and qbmm_output share: (a, b, lead, batch, b_batch, M, K, N), the operands dense."""
+  for name, t in (("a", a), ("b", b)):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int8 or not t.is_cuda or t.dim() < 2:
+      got = f"{t.dtype} {tuple(t.shape)} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+      raise TypeError(f"{who}: `{name}` must be an int8 device tensor of rank >= 2, got {got}")
+  lead = tuple(a.shape[:-2])
+  batch, b_batch = int(np.prod(lead, dtype=np.int64)), int(np.prod(tuple(b.shape[:-2]), dtype=np.int64))
+  k, m = (a.shape[-2], a.shape[-1]) if adj_x else (a.shape[-1], a.shape[-2])
+  n, kb = (b.shape[-2], b.shape[-1]) if adj_y else (b.shape[-1], b.shape[-2])
+  if k != kb:
+    raise ValueError(f"{who}: the operands disagree on K ({k} of {tuple(a.shape)}, {kb} of {tuple(b.shape)};"
+                     f" adj_x = {bool(adj_x)}, adj_y = {bool(adj_y)})")
+  if tuple(b.shape[:-2]) != lead and b_batch != 1:
+    raise ValueError(f"{who}: the batch dimensions of b {tuple(b.shape[:-2])} are neither those of a {lead} nor of"
+                     " product 1 (general broadcasting is not built)")
+  if k > QBMM_MAX_K:
+    raise ValueError(f"{who}: K = {k} exceeds {QBMM_MAX_K} (the int32 accumulator)")
+  for name, zp in (("a_zero_point", a_zero_point), ("b_zero_point", b_zero_point)):
+    if not -128 <= int(zp) <= 127:
+      raise ValueError(f"{who}: {name} = {zp} is outside int8")
+  # (no copy of a dense operand: a misaligned view is still dense, and the library routes on the address)
+  a = a if a.is_contiguous() else a.contiguous()
+  b = b if b.is_contiguous() else b.contiguous()
+  return a, b, lead, batch, (batch if tuple(b.shape[:-2]) == lead else 1), int(m), int(k), int(n)
+
+
+def _qbmm_workspace(batch: int, m: int, k: int, adj_x: bool, b_batch: int, n: int, adj_y: bool, za: int, zb: int):
+  """The operand sums and the transposed copy of every operand that is strided along K; nothing (a NULL workspace)
+  when there is neither a zero point nor such an operand."""
+  if za == 0 and zb == 0 and not adj_x and adj_y:
+    return None, 0
+  nbytes = _ffi.lib().mi355q_qbmm_workspace_bytes(batch, m, k, 1 if adj_x else 0, b_batch, n, 1 if adj_y else 0)
+  return rt.empty((max(nbytes, 1),), torch.uint8), nbytes
+
+
+def qbmm_forward(a: torch.Tensor, b: torch.Tensor, *, adj_x: bool, adj_y: bool, a_scale: torch.Tensor, a_zero_point: int,
+                 b_scale: torch.Tensor, b_zero_point: int, want_acc: bool = False):
+  """The integer BATCH_MATMUL product of two int8 device tensors of rank >= 2 that both carry a zero point:
+  acc[.., m, n] = Sum_k (a - a_zero_point) (b - b_zero_point) exact in int32 and y = float(acc) * (a_scale * b_scale),
+  float32 [.., M, N]. `a` is [.., M, K] ([.., K, M] with `adj_x`), `b` [.., K, N] ([.., N, K] with `adj_y`); the leading
+  dimensions of `a` are the batch, and `b` has the same ones or a batch product of 1 (one matrix for every batch).
+  `a_scale` holds 1 or batch * M float32 entries (per row: the dynamic mode), `b_scale` 1 or N. K <= 32768. Returns y,
+  or (y, acc int32) with `want_acc` (include/mi355q.h, "Integer batched matrix product"). Does not synchronize."""
+  rt.require_gpu()
+  who = "qbmm_forward"
+  za, zb = int(a_zero_point), int(b_zero_point)
+  a, b, lead, batch, b_batch, m, k, n = _qbmm_shapes(who, a, b, adj_x, adj_y, za, zb)
+  a_scale, b_scale = _f32(a_scale).view(-1), _f32(b_scale).view(-1)
+  if a_scale.numel() not in (1, batch * m):
+    raise ValueError(f"{who}: a_scale needs 1 or batch * M = {batch * m} entries (got {a_scale.numel()})")
+  if b_scale.numel() not in (1, n):
+    raise ValueError(f"{who}: b_scale needs 1 or N = {n} entries (got {b_scale.numel()})")
+  y = rt.empty(lead + (m, n), torch.float32)
+  acc = rt.empty(lead + (m, n), torch.int32) if want_acc else None
+  ws, nbytes = _qbmm_workspace(batch, m, k, adj_x, b_batch, n, adj_y, za, zb)
+  _ffi.check(_ffi.lib().mi355q_qbmm_forward_i8(rt.ptr(a), batch, m, k, 1 if adj_x else 0, rt.ptr(a_scale), a_scale.numel(),
+                                               za, rt.ptr(b), b_batch, n, 1 if adj_y else 0, rt.ptr(b_scale),
+                                               b_scale.numel(), zb, rt.ptr(y), rt.ptr(acc), rt.ptr(ws), nbytes,
+                                               rt.stream_ptr()))
+  return (y, acc) if want_acc else y
+
+
+def qbmm_output(a: torch.Tensor, b: torch.Tensor, *, adj_x: bool, adj_y: bool, a_zero_point: int, b_zero_point: int,
+                multiplier, shift, out_zero_point: int) -> torch.Tensor:
+  """What a static int8 BATCH_MATMUL op stores: int8 [.., M, N] = clamp(mbqm32(acc, M, s) + out_zero_point, -128, 127)
+  of qbmm_forward's accumulator, with qfc_output's fixed-point requantization; the op has neither a bias nor a fused
+  activation. `multiplier` / `shift` are host tables of 1 or N entries (quantize_multiplier), or qfc_multipliers'
+  result with `shift` None. Does not synchronize."""
+  rt.require_gpu()
+  who = "qbmm_output"
+  za, zb = int(a_zero_point), int(b_zero_point)
+  a, b, lead, batch, b_batch, m, k, n = _qbmm_shapes(who, a, b, adj_x, adj_y, za, zb)
+  tables = _qfc_output_tables(who, multiplier, shift, n, 8)
+  if not -128 <= int(out_zero_point) <= 127:
+    raise ValueError(f"{who}: out_zero_point = {out_zero_point} is outside int8")
+  q = rt.empty(lead + (m, n), torch.int8)
+  ws, nbytes = _qbmm_workspace(batch, m, k, adj_x, b_batch, n, adj_y, za, zb)
+  _ffi.check(_ffi.lib().mi355q_qbmm_output_i8(rt.ptr(a), batch, m, k, 1 if adj_x else 0, za, rt.ptr(b), b_batch, n,
+                                              1 if adj_y else 0, zb, rt.ptr(tables.multiplier), rt.ptr(tables.shift),
+                                              tables.multiplier.numel(), int(out_zero_point), rt.ptr(q), rt.ptr(ws), nbytes,
+                                              rt.stream_ptr()))
+  return q
+
+
 def sqdiff_cols(a: torch.Tensor, b: torch.Tensor, out: tuple | None = None):
   """(Sum_t (a - b)^2, Sum_t b^2) per column of float32 [n, cols] device tensors, float64 [cols] each, added in a
   fixed order (the same bits in every run). With `out` = an earlier result the sums are added onto it in place and

@@ -250,7 +250,8 @@ class Quantizer:
                                int16_activations: bool = False,
                                quantized_outputs: bool = False,
                                conv_2d: bool = False,
-                               depthwise_conv_2d: bool = False) -> model_validator.LayerExecutionComparison:
+                               depthwise_conv_2d: bool = False,
+                               batch_matmul: bool = False) -> model_validator.LayerExecutionComparison:
     """Executes every quantized FULLY_CONNECTED op of the last quantize() result in integers on the calibration
     samples and compares it with the float product: error = (1/n) ||Yq - Y||^2 per op with its signal, MSE, SNR,
     per-channel errors, token count and mode (model_validator.compare_layer_execution). Unlike
@@ -270,7 +271,11 @@ class Quantizer:
     rank-4 samples (ops.conv_patches): every entry gains `op`, and a conv entry `kernel`, `strides`, `dilations`,
     `padding` and `output_hw`, with `rows` the output channels, `d` = KH KW I and `tokens` the patch rows. With
     `depthwise_conv_2d` every DEPTHWISE_CONV_2D op is executed too, by a direct convolution (ops.dwconv_forward): an
-    entry has the keys of a conv entry with `op` = "DEPTHWISE_CONV_2D", `d` = KH KW, and `depth_multiplier`."""
+    entry has the keys of a conv entry with `op` = "DEPTHWISE_CONV_2D", `d` = KH KW, and `depth_multiplier`. With
+    `batch_matmul` every BATCH_MATMUL op is executed too, by the integer batched product (ops.qbmm_forward): a constant
+    right-hand side in the static, dynamic and weight-only modes, or two INT8 activations with a zero point each (the
+    attention products); an entry has `op` = "BATCH_MATMUL", `operands`, `adj_x`, `adj_y` and `batch`, `rows` = N and
+    `d` = K (model_validator.compare_layer_execution)."""
     quantized_model = self._result.quantized_model
     if quantized_model is None:
       raise ValueError("No quantized model available to validate.")
@@ -279,7 +284,7 @@ class Quantizer:
                                                       follow_input_transforms=follow_input_transforms,
                                                       int16_activations=int16_activations,
                                                       quantized_outputs=quantized_outputs, conv_2d=conv_2d,
-                                                      depthwise_conv_2d=depthwise_conv_2d)
+                                                      depthwise_conv_2d=depthwise_conv_2d, batch_matmul=batch_matmul)
     if save_folder:
       if model_name is None:
         model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"

@@ -1281,6 +1281,95 @@ int32_t mi355q_dwconv_output_i16(const int16_t* xq, int64_t N, int64_t H, int64_
                                  int32_t pad_top, int32_t pad_left, int64_t OH, int64_t OW, int64_t first_row,
                                  int64_t row_count, int16_t* q_out, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Integer batched matrix product (csrc/qbmm.hip): the BATCH_MATMUL op with
+ * int8 operands that BOTH carry a zero point, as the two attention products
+ * of a statically quantized transformer have them (Q K^T with adj_y, P V
+ * without). The arithmetic is this library's own definition, modelled on
+ * LiteRT's BATCH_MATMUL; agreement with LiteRT's kernels has not been checked,
+ * the claim is bit equality with the statement below.
+ *
+ * Statement. a is int8 [batch, M, K], or [batch, K, M] with adj_x; b is int8
+ * [b_batch, K, N], or [b_batch, N, K] with adj_y; b_batch is 1 or batch, and
+ * with b_batch = 1 the one matrix serves every batch (b' = 0, else b' = b).
+ *   acc[b,m,n] = Sum_k (A[b,m,k] - a_zero_point) (B[b',k,n] - b_zero_point)
+ * exact in int32: a term is at most 255 * 255 in magnitude, so K <= 32768
+ * keeps |acc| <= 2 130 739 200 < 2^31; a larger K is refused.
+ *   mi355q_qbmm_forward_i8:
+ *     y_out[b,m,n] = fl32( float(acc) * fl32(a_scale[.] * b_scale[.]) )
+ *   FULLY_CONNECTED's form. a_scale has 1 or batch M entries (entry b M + m:
+ *   the per-row scales of the dynamic mode, meaningful without adj_x), b_scale
+ *   1 or N. y_out is float32 [batch, M, N]; acc_out is NULL or int32
+ *   [batch, M, N].
+ *   mi355q_qbmm_output_i8:
+ *     q_out[b,m,n] = clamp(mbqm32(acc, M[.], s[.]) + out_zero_point, -128, 127)
+ *   int8 [batch, M, N], with the fixed-point requantization of
+ *   mi355q_qfc_output_i8 UNCHANGED (one piece of device code,
+ *   csrc/qfc_epilogue.h). BatchMatMulOptions has neither a bias nor a fused
+ *   activation, so the epilogue gets no bias and the full int8 range;
+ *   multiplier and shift have mcount in {1, N} entries. Only q_out is written.
+ *
+ * Routes; both give the same bits. MFMA route (K % 64 == 0, a and b 16-byte
+ * aligned, M % 16 == 0 with adj_x, N % 16 == 0 without adj_y): Sum a b on
+ * v_mfma_i32_16x16x64_i8 with the main loop and the tile of the
+ * FULLY_CONNECTED route (qfc_tile.h): a wave on 64 x 64 outputs, a workgroup
+ * of 2 x 2 waves on 128 x 128, the batch along the grid's z, both operands
+ * read contiguous along K, 16 consecutive k per lane. An operand that is
+ * strided along K (a with adj_x; b without adj_y, the default layout) is
+ * first TRANSPOSED into the workspace by a pre-pass (64 x 64 byte tiles
+ * through LDS, 16-byte loads and stores). Staging such an operand through LDS
+ * inside the product (16-byte loads, a 4 x 4 byte transpose with v_perm_b32,
+ * 16-byte read-back) was built and measured 5.3 - 6.6 x slower than
+ * transposing first (profiles/qbmm_staged_bench.json), so it was not
+ * kept. The zero points enter through operand sums,
+ *   acc = Sum a b - zb Sum_k a - za Sum_k b + K za zb,
+ * taken by a pre-pass into the workspace (Sum_k a only when zb != 0, Sum_k b
+ * only when za != 0; each sum is at most 2^22 in magnitude and exact in
+ * int32). Each of the four terms is at most 2^29 in magnitude and exact in
+ * int32, but a partial sum of them can pass 2^31: they are combined in
+ * uint32, whose wrap-around is defined, which gives the total modulo 2^32,
+ * and the total lies within int32 by the bound above. No intermediate needs
+ * int64. batch = 1 with (adj_x, adj_y) = (0, 1) and b_zero_point = 0 is the
+ * FULLY_CONNECTED problem and mi355q_qbmm_forward_i8 hands it to
+ * mi355q_qfc_forward_i8: same statement, same bits. Generic route (every other K, M, N or
+ * alignment, K = 1 and misaligned bases among them): one thread per output
+ * forms Sum (a - za)(b - zb) one element at a time in int32, which the bound
+ * keeps exact. Tile edges in M, N and the batch are guarded; no kernel uses
+ * scratch memory.
+ *
+ * Workspace. mi355q_qbmm_workspace_bytes is the most a call of these shapes
+ * can need: the two sums, plus a copy of every operand that is strided along
+ * K. With za = zb = 0 no sum is computed, and for (adj_x, adj_y) = (0, 1)
+ * the workspace may then be NULL; a non-zero zero point needs the sums' part
+ * on either route, and a K-strided operand on the MFMA route the whole, at a
+ * 16-byte aligned address.
+ *
+ * Refused before any launch: a negative batch, M, K, N or b_batch; a null a
+ * or b; a zero point outside int8 (MI355Q_BAD_ARG); b_batch outside
+ * {1, batch} (MI355Q_BAD_SHAPE); K > 32768 (MI355Q_UNSUPPORTED); a null
+ * a_scale, b_scale, y_out, multiplier, shift or q_out; a_scale_count outside
+ * {1, batch M}, b_scale_count or mcount outside {1, N}; out_zero_point
+ * outside int8; with a non-zero zero point a workspace that is NULL, too
+ * small for the sums or not 4-byte aligned (MI355Q_BAD_ARG). After those batch, M or N == 0
+ * enqueues nothing; K == 0 is the empty sum, acc = 0, on the generic route.
+ * On the MFMA route a workspace that is NULL, misaligned or too small for
+ * the transposed copies is MI355Q_BAD_ARG, more than 65535 batches or tiles
+ * of 128 rows of M MI355Q_UNSUPPORTED. mi355q_qbmm_mfma_route answers on the
+ * host, reading nothing, whether a call with these bases and shapes takes
+ * the MFMA route (1) or the generic one (0).
+ * ------------------------------------------------------------------------ */
+int64_t mi355q_qbmm_mfma_route(const void* a, int64_t M, int64_t K, int32_t adj_x, const void* b, int64_t N, int32_t adj_y);
+size_t mi355q_qbmm_workspace_bytes(int64_t batch, int64_t M, int64_t K, int32_t adj_x, int64_t b_batch, int64_t N,
+                                   int32_t adj_y);
+int32_t mi355q_qbmm_forward_i8(const int8_t* a, int64_t batch, int64_t M, int64_t K, int32_t adj_x, const float* a_scale,
+                               int64_t a_scale_count, int32_t a_zero_point, const int8_t* b, int64_t b_batch, int64_t N,
+                               int32_t adj_y, const float* b_scale, int64_t b_scale_count, int32_t b_zero_point,
+                               float* y_out, int32_t* acc_out, void* workspace, size_t workspace_bytes, void* stream);
+int32_t mi355q_qbmm_output_i8(const int8_t* a, int64_t batch, int64_t M, int64_t K, int32_t adj_x, int32_t a_zero_point,
+                              const int8_t* b, int64_t b_batch, int64_t N, int32_t adj_y, int32_t b_zero_point,
+                              const int32_t* multiplier, const int32_t* shift, int64_t mcount, int32_t out_zero_point,
+                              int8_t* q_out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif
