@@ -2616,6 +2616,10 @@ extern "C" int32_t mi355q_mse_scale_nd_f32(const float* x, int64_t outer, int64_
   if (outer == 0 || inner == 0) return fail(MI355Q_BAD_SHAPE, "empty reduction unit");
   if (inner > 0x7FFFFFFFLL - 64) return fail(MI355Q_UNSUPPORTED, "inner too large");
   if (!x || !scale_out) return fail(MI355Q_BAD_ARG, "null pointer");
+  if (channels == 1) {  // one channel: NumPy merges the axes and sums ONE contiguous vector (chunks of 8192 across the segments)
+    if (outer > (0x7FFFFFFFLL - 64) / inner) return fail(MI355Q_UNSUPPORTED, "one channel too long");
+    return mi355q_mse_scale_f32(x, 1, outer * inner, multiplier, scale_out, stream);
+  }
   hipStream_t st = as_stream(stream);
   if (inner == 1)
     hipLaunchKernelGGL(mse_scale_cols_kernel, dim3(static_cast<unsigned>((channels + 255) / 256)), dim3(256),

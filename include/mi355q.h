@@ -316,7 +316,8 @@ int32_t mi355q_octav_clip_nd_f32(const float* x, int64_t outer, int64_t channels
  * ------------------------------------------------------------------------ */
 int32_t mi355q_mse_scale_f32(const float* x, int64_t units, int64_t unit_len, float multiplier,
                              float* scale_out, void* stream);
-/* [outer, channels, inner] view, one scale per channel (see mi355q_octav_clip_nd_f32). */
+/* [outer, channels, inner] view, one scale per channel (see mi355q_octav_clip_nd_f32). channels == 1 is ONE contiguous
+ * unit of outer * inner elements, as NumPy sums it (it merges the axes: chunks of 8192 run across the segments). */
 int32_t mi355q_mse_scale_nd_f32(const float* x, int64_t outer, int64_t channels, int64_t inner,
                                 float multiplier, float* scale_out, void* stream);
 /* a14 whole: the scale of every contiguous unit AND its integers, q = clip(rint(x / scale[u])) with a zero zero point
