@@ -11,6 +11,18 @@
 // reference -- so only the order of the FP32 additions differs from sgemm
 // (tolerance class T2).
 //
+// What is exact, whatever the order: an impulse +-2^j at p gives +-2^j r (-1)^popcount(p & q) for every h (one product,
+// then additions of zeros); dense integers |x| < 2^(23 - log2 h) give the integer Sylvester product for h = 4^m (r is
+// a power of two and every partial sum fits float32). Dense floats equal, bit for bit, r-scaled inputs sent through
+// (u + v, u - v) stages over index bits in the order of the route (tests/hadamard_route_cases.py):
+//   fwht_kernel             0, 1, ..., L-1      h < 256, or x / out not 16-byte aligned (any h; one vector per block
+//                                               from h = 2048 on, 64 KiB of dynamic LDS at h = 16384)
+//   fwht_tile_kernel<12>    0, 1, 10, 11, 2..9  256 <= h <= 4096 (bits >= L skipped: the fwht_kernel order up to 1024)
+//   fwht_tile_kernel<13>    0, 1, 11, 12, 2..9, 10       h = 8192
+//   fwht_tile_kernel<14>    0, 1, 12, 13, 2..9, 10, 11   h = 16384
+// So from h = 2048 on the misaligned fallback differs in bits from the tile kernels (another order of the same
+// additions); mi355q_weight_delta_transformed_f32 takes its network from h alone.
+//
 // Both kernels are templates over a source (element e, or the four elements e .. e+3) and a sink (which receives
 // them). mi355q_hadamard_rotate_f32 instantiates plain float loads and stores. The effective-weight delta of the layer
 // output error, mi355q_weight_delta_transformed_f32, instantiates the SAME networks with a target dequantized in

@@ -58,9 +58,14 @@ def _rotate_in_hbm(tensor_content, axis: int, max_size: int | None = None):
     raise ValueError("Hadamard rotation is only supported for tensors with quantized"
                      " dimension 0 (rotate last dimension).")
   h = hadamard_size_for(tensor_content.shape[axis], max_size)
+  if h < 2:
+    # ref :118-129: _make_hadamard_matrix(1) is the 2x2 matrix and reshape(-1, 1) @ 2x2 raises in matmul. Rotating
+    # the flattened tensor in pairs instead would mix neighbouring rows and still report hadamard_size 1.
+    raise ValueError(f"Hadamard size would be 1 (last dimension {tensor_content.shape[axis]}, max_hadamard_size "
+                     f"{max_size}): there is nothing to rotate, the last dimension must be even and the cap >= 2.")
   x = uniform_quantize_tensor._as_f32_exact(tensor_content)  # pylint: disable=protected-access
   rt.require_gpu()
-  rotated = ops.hadamard_rotate(rt.to_device(x.reshape(-1)), max(h, 2) if h < 2 else h)
+  rotated = ops.hadamard_rotate(rt.to_device(x.reshape(-1)), h)
   return rt.HbmArray(rotated.reshape(tuple(tensor_content.shape))), h, np.ones(h, dtype=np.int8)
 
 
