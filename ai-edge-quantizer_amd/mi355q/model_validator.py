@@ -480,16 +480,23 @@ def _as_model(model) -> Any:
   return model if hasattr(model, "subgraphs") else _model(model)
 
 
-def _fully_connected_ops(m, sg_index: int):
-  """(op, input 0 name, weight tensor, output name) of every FULLY_CONNECTED op of a subgraph."""
+def _ops_of_kind(m, sg_index: int, builtin: int, present: tuple = ()):
+  """(op, input 0 name, input 1 tensor, output name) of every op of kind `builtin` of a subgraph that has two inputs,
+  those numbered in `present` not absent (-1)."""
   sg = m.subgraphs[sg_index]
   out = []
   for op in sg.operators or []:
-    if int(m.operatorCodes[op.opcodeIndex].builtinCode) != _FULLY_CONNECTED or len(op.inputs) < 2:
+    if (int(m.operatorCodes[op.opcodeIndex].builtinCode) != builtin or len(op.inputs) < 2
+        or any(op.inputs[i] < 0 for i in present)):
       continue
     out.append((op, schema.tensor_name(sg.tensors[op.inputs[0]]), sg.tensors[op.inputs[1]],
                 schema.tensor_name(sg.tensors[op.outputs[0]])))
   return out
+
+
+def _fully_connected_ops(m, sg_index: int):
+  """(op, input 0 name, weight tensor, output name) of every FULLY_CONNECTED op of a subgraph."""
+  return _ops_of_kind(m, sg_index, _FULLY_CONNECTED)
 
 
 def layer_hessians(float_model, samples: Iterable[dict], signature_key: Optional[str] = None) -> dict[str, dict]:
@@ -860,46 +867,54 @@ _CONV_OPTION_FIELDS = (("padding", "padding", "i8", 0), ("stride_w", "strideW", 
                        ("dilation_w_factor", "dilationWFactor", "i32", 1), ("dilation_h_factor", "dilationHFactor", "i32", 1))
 
 
+def _table_options(op, fields: tuple, options_type: int, marker_attr: str) -> Optional[dict]:
+  """The options table of an op as {name: int} over `fields`, (name, generated attribute, scalar code, default) in the
+  schema's field order: from an OpaqueTableT (what the flatbuffer layer keeps) by field id, with the schema's defaults
+  for absent fields, when the op's builtinOptionsType is `options_type`; from a decoded object that has `marker_attr`
+  by the generated API's attribute names; every default for an op without options. None when the op carries the
+  options of another op type."""
+  o = op.builtinOptions
+  if o is None:
+    return {name: default for name, _, _, default in fields}
+  if isinstance(o, tfl_flatbuffer.OpaqueTableT):
+    if int(getattr(op, "builtinOptionsType", 0) or 0) != options_type:
+      return None
+    return {name: int(o.scalar(i, code, default)) for i, (name, _, code, default) in enumerate(fields)}
+  if not hasattr(o, marker_attr):
+    return None
+  out = {}
+  for name, attr, _, default in fields:
+    v = getattr(o, attr, None)
+    out[name] = default if v is None else int(v)
+  return out
+
+
+def _fused_option(options_reader):
+  """An `option(op, field)` in _fc_option's form for an op kind whose options `options_reader` reads: its fused
+  activation (-1 under another op's options); FC-only fields (weightsFormat) are default."""
+  def option(op, field: str) -> int:
+    if field != "fusedActivationFunction":
+      return 0
+    options = options_reader(op)
+    return -1 if options is None else options["fused_activation_function"]
+  return option
+
+
 def conv_2d_options(op) -> Optional[dict]:
   """Conv2DOptions of a CONV_2D op as {padding (0 SAME, 1 VALID), stride_w, stride_h, fused_activation_function,
   dilation_w_factor, dilation_h_factor}, in the schema's field order (ids 0 to 5). The flatbuffer layer keeps the
   table as an OpaqueTableT, whose scalars are read by field id with the schema's defaults for absent fields (0, and 1
   for the dilations); a decoded object with the generated API's attribute names is read as well; an op without
   options has every default. None when the op carries the options of another op type."""
-  o = op.builtinOptions
-  if o is None:
-    return {name: default for name, _, _, default in _CONV_OPTION_FIELDS}
-  if isinstance(o, tfl_flatbuffer.OpaqueTableT):
-    if int(getattr(op, "builtinOptionsType", 0) or 0) != _CONV_2D_OPTIONS_TYPE:
-      return None
-    return {name: int(o.scalar(i, code, default)) for i, (name, _, code, default) in enumerate(_CONV_OPTION_FIELDS)}
-  if not hasattr(o, "strideW"):
-    return None
-  out = {}
-  for name, attr, _, default in _CONV_OPTION_FIELDS:
-    v = getattr(o, attr, None)
-    out[name] = default if v is None else int(v)
-  return out
+  return _table_options(op, _CONV_OPTION_FIELDS, _CONV_2D_OPTIONS_TYPE, "strideW")
 
 
-def _conv_option(op, field: str) -> int:
-  """_fc_option for a CONV_2D: its fused activation; FC-only fields (weightsFormat) are default."""
-  if field != "fusedActivationFunction":
-    return 0
-  options = conv_2d_options(op)
-  return -1 if options is None else options["fused_activation_function"]
+_conv_option = _fused_option(conv_2d_options)      # (_fc_option for a CONV_2D)
 
 
 def _conv_2d_ops(m, sg_index: int):
   """(op, input 0 name, filter tensor, output name) of every CONV_2D op of a subgraph."""
-  sg = m.subgraphs[sg_index]
-  out = []
-  for op in sg.operators or []:
-    if int(m.operatorCodes[op.opcodeIndex].builtinCode) != _CONV_2D or len(op.inputs) < 2 or op.inputs[1] < 0:
-      continue
-    out.append((op, schema.tensor_name(sg.tensors[op.inputs[0]]), sg.tensors[op.inputs[1]],
-                schema.tensor_name(sg.tensors[op.outputs[0]])))
-  return out
+  return _ops_of_kind(m, sg_index, _CONV_2D, present=(1,))
 
 
 # `depthwise_conv_2d`: DEPTHWISE_CONV_2D ops, executed by a direct convolution (csrc/dwconv.hip)
@@ -926,41 +941,15 @@ def depthwise_conv_2d_options(op) -> Optional[dict]:
   for absent fields (0, and 1 for the dilations; a depth_multiplier of 0 says nothing, converters leave it to the
   shapes), or from a decoded object with the generated API's attribute names; an op without options has every
   default. None when the op carries the options of another op type."""
-  o = op.builtinOptions
-  if o is None:
-    return {name: default for name, _, _, default in _DEPTHWISE_OPTION_FIELDS}
-  if isinstance(o, tfl_flatbuffer.OpaqueTableT):
-    if int(getattr(op, "builtinOptionsType", 0) or 0) != _DEPTHWISE_CONV_2D_OPTIONS_TYPE:
-      return None
-    return {name: int(o.scalar(i, code, default)) for i, (name, _, code, default) in enumerate(_DEPTHWISE_OPTION_FIELDS)}
-  if not hasattr(o, "depthMultiplier"):
-    return None
-  out = {}
-  for name, attr, _, default in _DEPTHWISE_OPTION_FIELDS:
-    v = getattr(o, attr, None)
-    out[name] = default if v is None else int(v)
-  return out
+  return _table_options(op, _DEPTHWISE_OPTION_FIELDS, _DEPTHWISE_CONV_2D_OPTIONS_TYPE, "depthMultiplier")
 
 
-def _depthwise_option(op, field: str) -> int:
-  """_conv_option for a DEPTHWISE_CONV_2D."""
-  if field != "fusedActivationFunction":
-    return 0
-  options = depthwise_conv_2d_options(op)
-  return -1 if options is None else options["fused_activation_function"]
+_depthwise_option = _fused_option(depthwise_conv_2d_options)      # (_conv_option for a DEPTHWISE_CONV_2D)
 
 
 def _depthwise_conv_2d_ops(m, sg_index: int):
   """(op, input 0 name, filter tensor, output name) of every DEPTHWISE_CONV_2D op of a subgraph."""
-  sg = m.subgraphs[sg_index]
-  out = []
-  for op in sg.operators or []:
-    if (int(m.operatorCodes[op.opcodeIndex].builtinCode) != _DEPTHWISE_CONV_2D or len(op.inputs) < 2 or op.inputs[0] < 0
-        or op.inputs[1] < 0):
-      continue
-    out.append((op, schema.tensor_name(sg.tensors[op.inputs[0]]), sg.tensors[op.inputs[1]],
-                schema.tensor_name(sg.tensors[op.outputs[0]])))
-  return out
+  return _ops_of_kind(m, sg_index, _DEPTHWISE_CONV_2D, present=(0, 1))
 
 
 # `batch_matmul`: BATCH_MATMUL ops, executed by the integer batched product (csrc/qbmm.hip)
@@ -994,13 +983,8 @@ def batch_matmul_options(op) -> Optional[dict]:
 def _batch_matmul_ops(m, sg_index: int):
   """(op, lhs tensor, rhs tensor, output name) of every BATCH_MATMUL op of a subgraph."""
   sg = m.subgraphs[sg_index]
-  out = []
-  for op in sg.operators or []:
-    if (int(m.operatorCodes[op.opcodeIndex].builtinCode) != _BATCH_MATMUL or len(op.inputs) < 2 or op.inputs[0] < 0
-        or op.inputs[1] < 0):
-      continue
-    out.append((op, sg.tensors[op.inputs[0]], sg.tensors[op.inputs[1]], schema.tensor_name(sg.tensors[op.outputs[0]])))
-  return out
+  return [(op, sg.tensors[op.inputs[0]], rhs, y_name)
+          for op, _, rhs, y_name in _ops_of_kind(m, sg_index, _BATCH_MATMUL, present=(0, 1))]
 
 
 def _bmm_geometry(a_shape, b_shape, adj_x: bool, adj_y: bool):
@@ -1020,18 +1004,8 @@ def _bmm_geometry(a_shape, b_shape, adj_x: bool, adj_y: bool):
   return batch, (batch if a_shape[:-2] == b_shape[:-2] else 1), m, k, n
 
 
-def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray,
-                 option=_fc_option):
-  """An OutputPlan, or the FINAL_SKIP_* reason there is none. `option(op, field)` reads an op's options
-  (_conv_option for a CONV_2D and _depthwise_option for a DEPTHWISE_CONV_2D, whose FC-only fields are default)."""
-  from . import ops
-  if option(fc, "weightsFormat") != 0 or option(ref_op, "weightsFormat") != 0:
-    return FINAL_SKIP_WEIGHTS_FORMAT
-  fused, float_fused = option(fc, "fusedActivationFunction"), option(ref_op, "fusedActivationFunction")
-  if fused not in ops.FUSED_ACTIVATION_NAMES or float_fused not in ops.FUSED_ACTIVATION_NAMES:
-    return FINAL_SKIP_ACTIVATION
-  # ---- the output tensor
-  y = tgt_sg.tensors[fc.outputs[0]]
+def _output_grid(y, bits: int):
+  """(s_y, zp_y) of the output tensor `y` of a static op with `bits`-bit activations, or FINAL_SKIP_OUTPUT."""
   q = y.quantization
   want = schema.TensorType.INT16 if bits == 16 else schema.TensorType.INT8
   if y.type != want or q is None or q.scale is None or len(q.scale) != 1:
@@ -1042,6 +1016,42 @@ def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x
   s_y = float(np.float32(q.scale[0]))
   if not (np.isfinite(s_y) and s_y > 0):
     return FINAL_SKIP_OUTPUT
+  return s_y, zp_y
+
+
+def _multiplier_table(s_x: float, w_scale: np.ndarray, s_y: float, bits: int):
+  """(multiplier, shift), int32 with one entry per entry of `w_scale`: the fixed-point form of s_x s_w / s_y, in
+  float64 from the float32 scales as they are stored; FINAL_SKIP_MULTIPLIER when one has none within the shift range
+  of an op with `bits`-bit activations."""
+  from . import ops
+  lo, hi = ops.QFC_SHIFT_RANGE[bits]
+  multiplier, shift = [], []
+  for s_w in np.asarray(w_scale, np.float32).reshape(-1).tolist():
+    try:
+      m_r, e_r = ops.quantize_multiplier(float(np.float32(s_x)) * float(s_w) / s_y)
+    except ValueError:
+      return FINAL_SKIP_MULTIPLIER
+    if not lo <= e_r <= hi:
+      return FINAL_SKIP_MULTIPLIER
+    multiplier.append(m_r)
+    shift.append(e_r)
+  return np.asarray(multiplier, np.int32), np.asarray(shift, np.int32)
+
+
+def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray,
+                 option=_fc_option):
+  """An OutputPlan, or the FINAL_SKIP_* reason there is none. `option(op, field)` reads an op's options
+  (_conv_option for a CONV_2D and _depthwise_option for a DEPTHWISE_CONV_2D, whose FC-only fields are default)."""
+  from . import ops
+  if option(fc, "weightsFormat") != 0 or option(ref_op, "weightsFormat") != 0:
+    return FINAL_SKIP_WEIGHTS_FORMAT
+  fused, float_fused = option(fc, "fusedActivationFunction"), option(ref_op, "fusedActivationFunction")
+  if fused not in ops.FUSED_ACTIVATION_NAMES or float_fused not in ops.FUSED_ACTIVATION_NAMES:
+    return FINAL_SKIP_ACTIVATION
+  grid = _output_grid(tgt_sg.tensors[fc.outputs[0]], bits)
+  if isinstance(grid, str):
+    return grid
+  s_y, zp_y = grid
   # ---- the two biases
   def constant(m, sg, op, ttype) -> Any:
     """The op's input 2 as a flat array of `ttype`, None when absent, False when it is something else."""
@@ -1059,25 +1069,13 @@ def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x
   float_bias = constant(ref, ref_sg, ref_op, schema.TensorType.FLOAT32)
   if float_bias is False:
     return FINAL_SKIP_FLOAT_BIAS
-  # ---- multipliers, in float64 from the float32 scales as they are stored
-  w_scale = np.asarray(w_scale, np.float32).reshape(-1)
-  if w_scale.size not in (1, rows):
+  if np.size(w_scale) not in (1, rows):
     return FINAL_SKIP_MULTIPLIER
-  lo, hi = ops.QFC_SHIFT_RANGE[bits]
-  multiplier, shift = [], []
-  for s_w in w_scale.tolist():
-    real = float(np.float32(s_x)) * float(s_w) / s_y
-    try:
-      m_r, e_r = ops.quantize_multiplier(real)
-    except ValueError:
-      return FINAL_SKIP_MULTIPLIER
-    if not lo <= e_r <= hi:
-      return FINAL_SKIP_MULTIPLIER
-    multiplier.append(m_r)
-    shift.append(e_r)
+  table = _multiplier_table(s_x, w_scale, s_y, bits)
+  if isinstance(table, str):
+    return table
   act_min, act_max = ops.activation_range(fused, s_y, zp_y, bits)
-  return OutputPlan(bits, bias, float_bias, np.asarray(multiplier, np.int32), np.asarray(shift, np.int32), s_y, zp_y,
-                    act_min, act_max, fused, float_fused)
+  return OutputPlan(bits, bias, float_bias, table[0], table[1], s_y, zp_y, act_min, act_max, fused, float_fused)
 
 
 class LayerExecutionKernels:
@@ -1108,11 +1106,24 @@ class LayerExecutionKernels:
   def rows(self, x, first: int, count: int):
     return x[first:first + count]
 
-  def sample4d(self, value):
-    """A rank-4 sample entry (array or device tensor) as a contiguous float32 [N, H, W, C] tensor (`conv_2d`)."""
+  @staticmethod
+  def _sample_as_it_is(value):
+    """sample4d and sample_nd (two names, since stand-ins override them one by one)."""
     import torch
     from . import runtime as rt
     return rt.on_device(rt.resident_sample(value), torch.float32).contiguous()
+
+  @staticmethod
+  def _grid(scale: float, zero_point: int) -> tuple:
+    """(float32 [1], int32 [1]) on the device: one scale and one zero point as ops.quantize / ops.dequantize read them."""
+    import torch
+    from . import runtime as rt
+    return (torch.tensor([scale], dtype=torch.float32, device=rt.device()),
+            torch.tensor([zero_point], dtype=torch.int32, device=rt.device()))
+
+  def sample4d(self, value):
+    """A rank-4 sample entry (array or device tensor) as a contiguous float32 [N, H, W, C] tensor (`conv_2d`)."""
+    return self._sample_as_it_is(value)
 
   def patches(self, x, kernel: tuple, strides: tuple, dilations: tuple, padding: str, pad_value, first: int, count: int):
     """Rows first .. first + count - 1 of the [N OH OW, KH KW C] patch rows of x [N, H, W, C], in x's own type
@@ -1173,9 +1184,7 @@ class LayerExecutionKernels:
   # (`batch_matmul`: operands of rank 3, [batch, ., .], the right-hand one with a batch of 1 or the left's)
   def sample_nd(self, value):
     """A sample entry of any rank (array or device tensor) as a contiguous float32 tensor of its own shape."""
-    import torch
-    from . import runtime as rt
-    return rt.on_device(rt.resident_sample(value), torch.float32).contiguous()
+    return self._sample_as_it_is(value)
 
   def bmm_constant(self, plan: ConstantPlan, shape: tuple):
     """(int8 [b_batch, ., .], float32 scales): the stored integers and the scales of an int8 constant."""
@@ -1220,11 +1229,8 @@ class LayerExecutionKernels:
     return ops.qfc_quantize_rows(x)
 
   def quantize_static(self, x, scale: float, zero_point: int):
-    import torch
     from . import ops
-    from . import runtime as rt
-    s = torch.tensor([scale], dtype=torch.float32, device=rt.device())
-    zp = torch.tensor([zero_point], dtype=torch.int32, device=rt.device())
+    s, zp = self._grid(scale, zero_point)
     return ops.quantize(x.contiguous(), 1, 1, x.numel(), s, zp, 8, False), s
 
   def forward(self, xq, x_scale, x_zero_point: int, target, rows: int, d: int):
@@ -1233,11 +1239,8 @@ class LayerExecutionKernels:
 
   def quantize_static16(self, x, scale: float):
     """(q int16 [n, d], its one scale): q = clip(rint(x / s_x), -32768, 32767), symmetric, ops.quantize as it stands."""
-    import torch
     from . import ops
-    from . import runtime as rt
-    s = torch.tensor([scale], dtype=torch.float32, device=rt.device())
-    zp = torch.tensor([0], dtype=torch.int32, device=rt.device())
+    s, zp = self._grid(scale, 0)
     return ops.quantize(x.contiguous(), 1, 1, x.numel(), s, zp, 16, False), s
 
   def forward16(self, xq, x_scale, target, rows: int, d: int):
@@ -1262,11 +1265,8 @@ class LayerExecutionKernels:
 
   def dequantize_output(self, q, scale: float, zero_point: int):
     """float32 [n, rows] = float32(q - zp_y) * s_y (ops.dequantize; the difference fits int16 for both types)."""
-    import torch
     from . import ops
-    from . import runtime as rt
-    s = torch.tensor([scale], dtype=torch.float32, device=rt.device())
-    zp = torch.tensor([zero_point], dtype=torch.int32, device=rt.device())
+    s, zp = self._grid(scale, zero_point)
     return ops.dequantize(q, 1, 1, q.numel(), s, zp, 16)
 
   def reference_output(self, y, bias, fused: int):
@@ -1441,763 +1441,653 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
   modelled on LiteRT's BATCH_MATMUL; agreement with LiteRT's kernels is unchecked. Every entry carries `op` whenever
   this or a conv keyword is on.
 """
-  kernels = kernels or LayerExecutionKernels()
-  samples = list(samples)
   ref, tgt = _as_model(reference_model), _as_model(target_model)
   sg_ref, _ = _signature_subgraph(ref, signature_key)
   sg_tgt, _ = _signature_subgraph(tgt, signature_key)
-  tgt_sg = tgt.subgraphs[sg_tgt]
-  producers = _producers(tgt_sg)
-  producer_op: dict[str, Any] = {}
-  for op in tgt_sg.operators or []:
-    for o in op.outputs:
-      producer_op.setdefault(schema.tensor_name(tgt_sg.tensors[o]), op)
-
-  def code(op) -> int:
-    return int(tgt.operatorCodes[op.opcodeIndex].builtinCode)
-
-  def name(index) -> Optional[str]:
-    return schema.tensor_name(tgt_sg.tensors[index]) if index is not None and index >= 0 else None
-
+  graph = _TargetGraph.of(tgt, tgt.subgraphs[sg_tgt])
+  run = _ExecutionRun(ref, sg_ref, list(samples), kernels or LayerExecutionKernels(), follow_input_transforms,
+                      int16_activations, quantized_outputs, op_key=conv_2d or depthwise_conv_2d or batch_matmul)
   out = LayerExecutionComparison(signature_key)
-  for ref_op, x_name, w, y_name in _fully_connected_ops(ref, sg_ref):
-    w_name = schema.tensor_name(w)
-    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 2):
-      out.skipped[y_name] = SKIP_WEIGHT
-      continue
-    rows, d = int(w.shape[0]), int(w.shape[1])
-    fc = producer_op.get(y_name)
-    if fc is None or code(fc) != _FULLY_CONNECTED or len(fc.inputs) < 2 or fc.inputs[0] < 0 or fc.inputs[1] < 0:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    # ---- the weight the target op reads: the integer constant itself, or a DEQUANTIZE of it
-    read = tgt_sg.tensors[fc.inputs[1]]
-    target, through_dequantize = read, False
-    if not _has_data(tgt.buffers, read):
-      deq = producers.get(int(fc.inputs[1]))
-      if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
-        out.skipped[y_name] = SKIP_TARGET
-        continue
-      target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
-    if schema.tensor_name(target) != w_name or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    if target.type in (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16):
-      out.skipped[y_name] = SKIP_FLOAT_TARGET
-      continue
-    # ---- the activation it reads
-    x_in = tgt_sg.tensors[fc.inputs[0]]
-    if x_in.type == schema.TensorType.INT16 and not int16_activations:
-      out.skipped[y_name] = SKIP_INT16
-      continue
-    transform = (TRANSFORM_NONE, None, 0)
-    x_quant = None
-    activation_bits = None
-    if x_in.type in (schema.TensorType.INT8, schema.TensorType.INT16):
-      q = x_in.quantization
-      source = name(fc.inputs[0])
-      quantize = producers.get(int(fc.inputs[0]))
-      if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
-        source = name(quantize.inputs[0])
-      if q is None or q.scale is None or len(q.scale) != 1 or source != x_name or through_dequantize:
-        out.skipped[y_name] = SKIP_INPUT
-        continue
-      zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
-      activation_bits = 16 if x_in.type == schema.TensorType.INT16 else 8
-      if activation_bits == 16 and zero_point != 0:
-        out.skipped[y_name] = SKIP_INPUT
-        continue
-      x_quant = (float(np.float32(q.scale[0])), zero_point)
-      mode = MODE_STATIC
-    elif x_in.type == schema.TensorType.FLOAT32:
-      mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
-      if name(fc.inputs[0]) != x_name:
-        found = _input_transform(tgt, tgt_sg, producers, fc, x_name, d) if follow_input_transforms else None
-        if found is None:
-          out.skipped[y_name] = SKIP_INPUT
-          continue
-        transform = found
-    else:
-      out.skipped[y_name] = SKIP_INPUT
-      continue
-    values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
-    plan = _target_plan(w_name, values, tgt, target)
-    if plan is None or not plan.dequantized:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    if plan.kind not in ("i8", "i4", "i2"):
-      out.skipped[y_name] = SKIP_KIND
-      continue
-    if plan.scale is None:
-      _read_blockwise_scales(plan, tgt, tgt_sg.tensors, target)
-    if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
-      out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
-      continue
-    present = [s[x_name] for s in samples if x_name in s]
-    if not present:
-      out.skipped[y_name] = SKIP_NO_SAMPLE
-      continue
-    if any(int(np.prod(v.shape)) % d for v in present):
-      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
-      continue
-    w_dev = kernels.weight(values, rows, d)
-    t_dev = kernels.target(plan)
-    dq_dev = kernels.dequantized(t_dev, rows, d) if mode == MODE_WEIGHT_ONLY else None
-    final, final_sums, bias_dev, float_bias_dev = None, None, None, None
-    if quantized_outputs and mode == MODE_STATIC:
-      final = _output_plan(ref, ref.subgraphs[sg_ref], ref_op, tgt, tgt_sg, fc, rows, activation_bits, x_quant[0],
-                           plan.scale)
-    if isinstance(final, OutputPlan):
-      bias_dev = None if final.bias is None else kernels.bias(final.bias)
-      float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
-    sums, tokens = None, 0
-    for value in present:
-      x = kernels.sample(value, d)
-      n = int(x.shape[0])
-      for first in range(0, n, EXECUTION_CHUNK_ROWS):
-        xc = kernels.rows(x, first, min(EXECUTION_CHUNK_ROWS, n - first))
-        y = kernels.gemm(xc, w_dev)
-        xt = xc if transform[0] == TRANSFORM_NONE else kernels.transform(xc, *transform)
-        if mode == MODE_WEIGHT_ONLY:
-          yq = kernels.gemm(xt, dq_dev)
-        elif mode == MODE_DYNAMIC:
-          xq, x_scale = kernels.quantize_dynamic(xt)
-          yq = kernels.forward(xq, x_scale, 0, t_dev, rows, d)
-        elif activation_bits == 16:
-          xq, x_scale = kernels.quantize_static16(xt, x_quant[0])
-          yq = kernels.forward16(xq, x_scale, t_dev, rows, d)
-        else:
-          xq, x_scale = kernels.quantize_static(xt, *x_quant)
-          yq = kernels.forward(xq, x_scale, x_quant[1], t_dev, rows, d)
-        sums = kernels.sqdiff(yq, y, sums)
-        if isinstance(final, OutputPlan):
-          if activation_bits == 16:
-            q_out = kernels.output16(xq, t_dev, rows, d, bias_dev, final.multiplier, final.shift, final.act_min,
-                                     final.act_max)
-          else:
-            q_out = kernels.output(xq, x_quant[1], t_dev, rows, d, bias_dev, final.multiplier, final.shift,
-                                   final.zero_point, final.act_min, final.act_max)
-          final_sums = kernels.sqdiff(kernels.dequantize_output(q_out, final.scale, final.zero_point),
-                                      kernels.reference_output(y, float_bias_dev, final.float_fused), final_sums)
-      tokens += n
-    if sums is None:          # (every sample of the input was empty)
-      out.skipped[y_name] = SKIP_NO_SAMPLE
-      continue
-    sq_diff, sq_ref = kernels.host(sums)
-    per_channel = np.asarray(sq_diff, np.float64) / tokens
-    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
-    mse = error / rows
-    out.results[y_name] = {"weight": w_name, "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
-                           "signal": signal, "error": error, "output_mse": mse,
-                           "output_snr": (signal / rows) / (mse + 1e-9), "per_channel_error": per_channel}
-    if follow_input_transforms:
-      out.results[y_name].update(input_transform=transform[0], hadamard_size=transform[2])
-    if int16_activations:
-      out.results[y_name]["activation_bits"] = activation_bits
-    if quantized_outputs:
-      entry = out.results[y_name]
-      entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
-      if isinstance(final, OutputPlan):
-        from . import ops
-        f_diff, f_ref = kernels.host(final_sums)
-        f_channel = np.asarray(f_diff, np.float64) / tokens
-        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
-        f_mse = f_error / rows
-        entry.update(fused_activation=ops.FUSED_ACTIVATION_NAMES[final.fused], final_signal=f_signal,
-                     final_error=f_error, final_output_mse=f_mse, final_output_snr=(f_signal / rows) / (f_mse + 1e-9),
-                     final_per_channel_error=f_channel)
-      elif final is not None:
-        entry["final_skipped"] = final
-    if conv_2d or depthwise_conv_2d or batch_matmul:
-      out.results[y_name]["op"] = "FULLY_CONNECTED"
-  if not (conv_2d or depthwise_conv_2d or batch_matmul):
-    return out
-
-  # ---- CONV_2D: the same product on patch rows (the docstring's section on `conv_2d`)
-  from . import ops
-  for ref_op, x_name, w, y_name in (_conv_2d_ops(ref, sg_ref) if conv_2d else []):
-    w_name = schema.tensor_name(w)
-    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
-        or min(int(v) for v in w.shape) < 1):
-      out.skipped[y_name] = SKIP_CONV_FILTER
-      continue
-    rows, kh, kw, channels = (int(v) for v in w.shape)
-    d = kh * kw * channels
-    conv = producer_op.get(y_name)
-    if conv is None or code(conv) != _CONV_2D or len(conv.inputs) < 2 or conv.inputs[0] < 0 or conv.inputs[1] < 0:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    options, float_options = conv_2d_options(conv), conv_2d_options(ref_op)
-    geometry = ("padding", "stride_h", "stride_w", "dilation_h_factor", "dilation_w_factor")
-    if (options is None or float_options is None or any(options[k] != float_options[k] for k in geometry)
-        or options["padding"] not in ops.CONV_PADDING_NAMES or min(options[k] for k in geometry[1:]) < 1):
-      out.skipped[y_name] = SKIP_CONV_OPTIONS
-      continue
-    strides, dilations = (options["stride_h"], options["stride_w"]), (options["dilation_h_factor"], options["dilation_w_factor"])
-    padding = ops.CONV_PADDING_NAMES[options["padding"]]
-    # ---- the filter the target op reads: the integer constant itself, or a DEQUANTIZE of it
-    read = tgt_sg.tensors[conv.inputs[1]]
-    target, through_dequantize = read, False
-    if not _has_data(tgt.buffers, read):
-      deq = producers.get(int(conv.inputs[1]))
-      if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
-        out.skipped[y_name] = SKIP_TARGET
-        continue
-      target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
-    if schema.tensor_name(target) != w_name or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    if target.type in (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16):
-      out.skipped[y_name] = SKIP_FLOAT_TARGET
-      continue
-    # ---- the activation it reads (follow_input_transforms does not apply: a conv behind an inserted op is skipped)
-    x_in = tgt_sg.tensors[conv.inputs[0]]
-    if x_in.type == schema.TensorType.INT16 and not int16_activations:
-      out.skipped[y_name] = SKIP_INT16
-      continue
-    x_quant, activation_bits = None, None
-    if x_in.type in (schema.TensorType.INT8, schema.TensorType.INT16):
-      q = x_in.quantization
-      source = name(conv.inputs[0])
-      quantize = producers.get(int(conv.inputs[0]))
-      if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
-        source = name(quantize.inputs[0])
-      if q is None or q.scale is None or len(q.scale) != 1 or source != x_name or through_dequantize:
-        out.skipped[y_name] = SKIP_INPUT
-        continue
-      zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
-      activation_bits = 16 if x_in.type == schema.TensorType.INT16 else 8
-      if (activation_bits == 16 and zero_point != 0) or not -128 <= zero_point <= 127:
-        out.skipped[y_name] = SKIP_INPUT
-        continue
-      x_quant = (float(np.float32(q.scale[0])), zero_point)
-      mode = MODE_STATIC
-    elif x_in.type == schema.TensorType.FLOAT32 and name(conv.inputs[0]) == x_name:
-      mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
-    else:
-      out.skipped[y_name] = SKIP_INPUT
-      continue
-    # ---- the filter as a [O, K] constant: K = KH KW I is contiguous per output channel
-    values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
-    plan = _target_plan(w_name, values, tgt, target)
-    if plan is None or not plan.dequantized:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    if plan.kind not in ("i8", "i4", "i2"):
-      out.skipped[y_name] = SKIP_KIND
-      continue
-    if plan.scale is None:
-      out.skipped[y_name] = SKIP_CONV_BLOCKWISE
-      continue
-    if not (plan.channels == 1 or (plan.channels == rows and plan.inner == d)):
-      out.skipped[y_name] = SKIP_TARGET      # (per-channel scales along another dimension than 0)
-      continue
-    if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
-      out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
-      continue
-    present = [s[x_name] for s in samples if x_name in s]
-    if not present:
-      out.skipped[y_name] = SKIP_NO_SAMPLE
-      continue
-    if any(len(v.shape) != 4 for v in present):
-      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
-      continue
-    if any(int(v.shape[3]) != channels for v in present):
-      out.skipped[y_name] = SKIP_CONV_GROUPS
-      continue
-    try:
-      if d > ops.QFC_MAX_D:
-        raise ValueError("K")
-      shapes = [ops.conv_geometry(int(v.shape[1]), int(v.shape[2]), kh, kw, strides, dilations, padding) for v in present
-                if int(v.shape[0]) > 0]
-    except ValueError:
-      out.skipped[y_name] = SKIP_CONV_GEOMETRY
-      continue
-    if not shapes:            # (every sample of the input was empty)
-      out.skipped[y_name] = SKIP_NO_SAMPLE
-      continue
-    w_dev = kernels.weight(values, rows, d)
-    t_dev = kernels.target(plan)
-    dq_dev = kernels.dequantized(t_dev, rows, d) if mode == MODE_WEIGHT_ONLY else None
-    final, final_sums, bias_dev, float_bias_dev = None, None, None, None
-    if quantized_outputs and mode == MODE_STATIC:
-      final = _output_plan(ref, ref.subgraphs[sg_ref], ref_op, tgt, tgt_sg, conv, rows, activation_bits, x_quant[0],
-                           plan.scale, option=_conv_option)
-    if isinstance(final, OutputPlan):
-      bias_dev = None if final.bias is None else kernels.bias(final.bias)
-      float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
-    sums, tokens = None, 0
-    gather = (kh, kw), strides, dilations, padding
-    for value in present:
-      if int(value.shape[0]) == 0:
-        continue
-      x = kernels.sample4d(value)
-      oh, ow, _, _ = ops.conv_geometry(int(x.shape[1]), int(x.shape[2]), kh, kw, strides, dilations, padding)
-      n = int(x.shape[0]) * oh * ow
-      # the whole sample is quantized ONCE and the patches are gathered from the integer tensor, padded with the zero
-      # point: q(0.0) = zp_x, so these are the bits of quantizing float patches padded with 0.0
-      if mode == MODE_DYNAMIC:
-        xq_all, scale_rows = kernels.quantize_dynamic_images(x, oh * ow)
-        pad = 0
-      elif mode == MODE_STATIC and activation_bits == 16:
-        xq_all, x_scale = kernels.quantize_static16(x, x_quant[0])
-        pad = 0
-      elif mode == MODE_STATIC:
-        xq_all, x_scale = kernels.quantize_static(x, *x_quant)
-        pad = x_quant[1]
-      for first in range(0, n, EXECUTION_CHUNK_ROWS):
-        count = min(EXECUTION_CHUNK_ROWS, n - first)
-        xc = kernels.patches(x, *gather, 0.0, first, count)
-        y = kernels.gemm(xc, w_dev)
-        if mode == MODE_WEIGHT_ONLY:
-          yq = kernels.gemm(xc, dq_dev)
-        else:
-          xq = kernels.patches(xq_all, *gather, pad, first, count)
-          if mode == MODE_DYNAMIC:
-            yq = kernels.forward(xq, kernels.rows(scale_rows, first, count), 0, t_dev, rows, d)
-          elif activation_bits == 16:
-            yq = kernels.forward16(xq, x_scale, t_dev, rows, d)
-          else:
-            yq = kernels.forward(xq, x_scale, x_quant[1], t_dev, rows, d)
-        sums = kernels.sqdiff(yq, y, sums)
-        if isinstance(final, OutputPlan):
-          if activation_bits == 16:
-            q_out = kernels.output16(xq, t_dev, rows, d, bias_dev, final.multiplier, final.shift, final.act_min,
-                                     final.act_max)
-          else:
-            q_out = kernels.output(xq, x_quant[1], t_dev, rows, d, bias_dev, final.multiplier, final.shift,
-                                   final.zero_point, final.act_min, final.act_max)
-          final_sums = kernels.sqdiff(kernels.dequantize_output(q_out, final.scale, final.zero_point),
-                                      kernels.reference_output(y, float_bias_dev, final.float_fused), final_sums)
-      tokens += n
-    sq_diff, sq_ref = kernels.host(sums)
-    per_channel = np.asarray(sq_diff, np.float64) / tokens
-    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
-    mse = error / rows
-    entry = out.results[y_name] = {
-        "op": "CONV_2D", "weight": w_name, "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
-        "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations), "padding": padding,
-        "output_hw": [shapes[0][0], shapes[0][1]],
-        "signal": signal, "error": error, "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
-        "per_channel_error": per_channel}
-    if follow_input_transforms:
-      entry.update(input_transform=TRANSFORM_NONE, hadamard_size=0)
-    if int16_activations:
-      entry["activation_bits"] = activation_bits
-    if quantized_outputs:
-      entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
-      if isinstance(final, OutputPlan):
-        f_diff, f_ref = kernels.host(final_sums)
-        f_channel = np.asarray(f_diff, np.float64) / tokens
-        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
-        f_mse = f_error / rows
-        entry.update(fused_activation=ops.FUSED_ACTIVATION_NAMES[final.fused], final_signal=f_signal,
-                     final_error=f_error, final_output_mse=f_mse, final_output_snr=(f_signal / rows) / (f_mse + 1e-9),
-                     final_per_channel_error=f_channel)
-      elif final is not None:
-        entry["final_skipped"] = final
-  # ---- DEPTHWISE_CONV_2D: a direct convolution, no patch rows (the docstring's section on `depthwise_conv_2d`)
-  for ref_op, x_name, w, y_name in (_depthwise_conv_2d_ops(ref, sg_ref) if depthwise_conv_2d else []):
-    w_name = schema.tensor_name(w)
-    if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
-        or int(w.shape[0]) != 1 or min(int(v) for v in w.shape) < 1):
-      out.skipped[y_name] = SKIP_DEPTHWISE_FILTER
-      continue
-    _, kh, kw, rows = (int(v) for v in w.shape)
-    d = kh * kw
-    conv = producer_op.get(y_name)
-    if (conv is None or code(conv) != _DEPTHWISE_CONV_2D or len(conv.inputs) < 2 or conv.inputs[0] < 0
-        or conv.inputs[1] < 0):
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    options, float_options = depthwise_conv_2d_options(conv), depthwise_conv_2d_options(ref_op)
-    geometry = ("padding", "stride_h", "stride_w", "dilation_h_factor", "dilation_w_factor")
-    if options is None or float_options is None:
-      out.skipped[y_name] = SKIP_CONV_OPTIONS
-      continue
-    if any(options[k] != float_options[k] for k in geometry + ("depth_multiplier",)):
-      out.skipped[y_name] = SKIP_DEPTHWISE_MISMATCH
-      continue
-    if options["padding"] not in ops.CONV_PADDING_NAMES or min(options[k] for k in geometry[1:]) < 1:
-      out.skipped[y_name] = SKIP_CONV_OPTIONS
-      continue
-    strides, dilations = (options["stride_h"], options["stride_w"]), (options["dilation_h_factor"], options["dilation_w_factor"])
-    padding = ops.CONV_PADDING_NAMES[options["padding"]]
-    # ---- the filter the target op reads: the integer constant itself, or a DEQUANTIZE of it
-    read = tgt_sg.tensors[conv.inputs[1]]
-    target, through_dequantize = read, False
-    if not _has_data(tgt.buffers, read):
-      deq = producers.get(int(conv.inputs[1]))
-      if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
-        out.skipped[y_name] = SKIP_TARGET
-        continue
-      target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
-    if schema.tensor_name(target) != w_name or not _has_data(tgt.buffers, target) or _numel(target) != rows * d:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    if target.type in (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16):
-      out.skipped[y_name] = SKIP_FLOAT_TARGET
-      continue
-    # ---- the activation it reads (as for CONV_2D: an op behind an inserted op is skipped)
-    x_in = tgt_sg.tensors[conv.inputs[0]]
-    if x_in.type == schema.TensorType.INT16 and not int16_activations:
-      out.skipped[y_name] = SKIP_INT16
-      continue
-    x_quant, activation_bits = None, None
-    if x_in.type in (schema.TensorType.INT8, schema.TensorType.INT16):
-      q = x_in.quantization
-      source = name(conv.inputs[0])
-      quantize = producers.get(int(conv.inputs[0]))
-      if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
-        source = name(quantize.inputs[0])
-      if q is None or q.scale is None or len(q.scale) != 1 or source != x_name or through_dequantize:
-        out.skipped[y_name] = SKIP_INPUT
-        continue
-      zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
-      activation_bits = 16 if x_in.type == schema.TensorType.INT16 else 8
-      if (activation_bits == 16 and zero_point != 0) or not -128 <= zero_point <= 127:
-        out.skipped[y_name] = SKIP_INPUT
-        continue
-      x_quant = (float(np.float32(q.scale[0])), zero_point)
-      mode = MODE_STATIC
-    elif x_in.type == schema.TensorType.FLOAT32 and name(conv.inputs[0]) == x_name:
-      mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
-    else:
-      out.skipped[y_name] = SKIP_INPUT
-      continue
-    # ---- the filter as a [KH KW, O] constant: the stored bytes of [1, KH, KW, O]
-    values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
-    plan = _target_plan(w_name, values, tgt, target)
-    if plan is None or not plan.dequantized:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    if plan.kind != "i8":
-      out.skipped[y_name] = SKIP_DEPTHWISE_KIND
-      continue
-    if plan.scale is None:
-      out.skipped[y_name] = SKIP_DEPTHWISE_BLOCKWISE
-      continue
-    if (not (plan.channels == 1 or (plan.channels == rows and plan.inner == 1))
-        or np.asarray(plan.scale).size != plan.channels):      # (O scales along dimension 0, of size 1, read as one)
-      out.skipped[y_name] = SKIP_DEPTHWISE_SCALE_AXIS
-      continue
-    if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
-      out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
-      continue
-    present = [s[x_name] for s in samples if x_name in s]
-    if not present:
-      out.skipped[y_name] = SKIP_NO_SAMPLE
-      continue
-    if any(len(v.shape) != 4 for v in present):
-      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
-      continue
-    channels = int(present[0].shape[3])
-    if (channels < 1 or any(int(v.shape[3]) != channels for v in present) or rows % channels
-        or options["depth_multiplier"] not in (0, rows // channels)):
-      out.skipped[y_name] = SKIP_DEPTHWISE_MULTIPLIER
-      continue
-    multiplier = rows // channels
-    try:
-      if d > ops.DWCONV_MAX_TAPS:
-        raise ValueError("taps")
-      shapes = [ops.conv_geometry(int(v.shape[1]), int(v.shape[2]), kh, kw, strides, dilations, padding) for v in present
-                if int(v.shape[0]) > 0]
-    except ValueError:
-      out.skipped[y_name] = SKIP_CONV_GEOMETRY
-      continue
-    if not shapes:            # (every sample of the input was empty)
-      out.skipped[y_name] = SKIP_NO_SAMPLE
-      continue
-    w_dev = kernels.weight(values, d, rows)
-    t_dev = kernels.target(plan)
-    dq_dev = kernels.dequantized(t_dev, d, rows) if mode == MODE_WEIGHT_ONLY else None
-    final, final_sums, bias_dev, float_bias_dev = None, None, None, None
-    if quantized_outputs and mode == MODE_STATIC:
-      final = _output_plan(ref, ref.subgraphs[sg_ref], ref_op, tgt, tgt_sg, conv, rows, activation_bits, x_quant[0],
-                           plan.scale, option=_depthwise_option)
-    if isinstance(final, OutputPlan):
-      bias_dev = None if final.bias is None else kernels.bias(final.bias)
-      float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
-    sums, tokens = None, 0
-    where = (kh, kw), multiplier, strides, dilations, padding
-    for value in present:
-      if int(value.shape[0]) == 0:
-        continue
-      x = kernels.sample4d(value)
-      oh, ow, _, _ = ops.conv_geometry(int(x.shape[1]), int(x.shape[2]), kh, kw, strides, dilations, padding)
-      n = int(x.shape[0]) * oh * ow
-      # the sample is quantized ONCE; a tap outside the image is skipped, which is what a pad element q(0.0) = zp_x adds
-      if mode == MODE_DYNAMIC:
-        xq_all, x_scale = kernels.quantize_dynamic_images(x, 1)      # (one scale per image)
-      elif mode == MODE_STATIC and activation_bits == 16:
-        xq_all, x_scale = kernels.quantize_static16(x, x_quant[0])
-      elif mode == MODE_STATIC:
-        xq_all, x_scale = kernels.quantize_static(x, *x_quant)
-      for first in range(0, n, EXECUTION_CHUNK_ROWS):
-        count = min(EXECUTION_CHUNK_ROWS, n - first)
-        y = kernels.depthwise_float(x, w_dev, *where, first, count)
-        if mode == MODE_WEIGHT_ONLY:
-          yq = kernels.depthwise_float(x, dq_dev, *where, first, count)
-        elif mode == MODE_DYNAMIC:
-          yq = kernels.depthwise_forward(xq_all, x_scale, 0, t_dev, *where, first, count)
-        elif activation_bits == 16:
-          yq = kernels.depthwise_forward16(xq_all, x_scale, t_dev, *where, first, count)
-        else:
-          yq = kernels.depthwise_forward(xq_all, x_scale, x_quant[1], t_dev, *where, first, count)
-        sums = kernels.sqdiff(yq, y, sums)
-        if isinstance(final, OutputPlan):
-          if activation_bits == 16:
-            q_out = kernels.depthwise_output16(xq_all, t_dev, *where, bias_dev, final.multiplier, final.shift,
-                                               final.act_min, final.act_max, first, count)
-          else:
-            q_out = kernels.depthwise_output(xq_all, x_quant[1], t_dev, *where, bias_dev, final.multiplier, final.shift,
-                                             final.zero_point, final.act_min, final.act_max, first, count)
-          final_sums = kernels.sqdiff(kernels.dequantize_output(q_out, final.scale, final.zero_point),
-                                      kernels.reference_output(y, float_bias_dev, final.float_fused), final_sums)
-      tokens += n
-    sq_diff, sq_ref = kernels.host(sums)
-    per_channel = np.asarray(sq_diff, np.float64) / tokens
-    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
-    mse = error / rows
-    entry = out.results[y_name] = {
-        "op": "DEPTHWISE_CONV_2D", "weight": w_name, "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
-        "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations), "padding": padding,
-        "output_hw": [shapes[0][0], shapes[0][1]], "depth_multiplier": multiplier,
-        "signal": signal, "error": error, "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
-        "per_channel_error": per_channel}
-    if follow_input_transforms:
-      entry.update(input_transform=TRANSFORM_NONE, hadamard_size=0)
-    if int16_activations:
-      entry["activation_bits"] = activation_bits
-    if quantized_outputs:
-      entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
-      if isinstance(final, OutputPlan):
-        f_diff, f_ref = kernels.host(final_sums)
-        f_channel = np.asarray(f_diff, np.float64) / tokens
-        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
-        f_mse = f_error / rows
-        entry.update(fused_activation=ops.FUSED_ACTIVATION_NAMES[final.fused], final_signal=f_signal,
-                     final_error=f_error, final_output_mse=f_mse, final_output_snr=(f_signal / rows) / (f_mse + 1e-9),
-                     final_per_channel_error=f_channel)
-      elif final is not None:
-        entry["final_skipped"] = final
+  _fully_connected_entries(out, graph, run)
+  if conv_2d:
+    _conv_2d_entries(out, graph, run)
+  if depthwise_conv_2d:
+    _depthwise_conv_2d_entries(out, graph, run)
   if batch_matmul:
-    _batch_matmul_entries(out, ref, sg_ref, tgt, tgt_sg, producers, producer_op, samples, kernels, quantized_outputs,
-                          follow_input_transforms, int16_activations)
+    _batch_matmul_entries(out, graph, run)
   return out
 
 
-def _batch_matmul_entries(out, ref, sg_ref, tgt, tgt_sg, producers, producer_op, samples, kernels, quantized_outputs,
-                          follow_input_transforms, int16_activations) -> None:
-  """The BATCH_MATMUL entries of compare_layer_execution (its docstring's section on `batch_matmul`)."""
+@dataclasses.dataclass
+class _TargetGraph:
+  """The quantized model's subgraph as the readers below walk it."""
+  tgt: Any
+  tgt_sg: Any
+  producers: dict        # tensor index -> the op that writes it
+  producer_op: dict      # output tensor name -> the op that writes it
+
+  @classmethod
+  def of(cls, tgt, tgt_sg) -> "_TargetGraph":
+    producer_op: dict[str, Any] = {}
+    for op in tgt_sg.operators or []:
+      for o in op.outputs:
+        producer_op.setdefault(schema.tensor_name(tgt_sg.tensors[o]), op)
+    return cls(tgt, tgt_sg, _producers(tgt_sg), producer_op)
+
+  def code(self, op) -> int:
+    return int(self.tgt.operatorCodes[op.opcodeIndex].builtinCode)
+
+  def name(self, index) -> Optional[str]:
+    return schema.tensor_name(self.tgt_sg.tensors[index]) if index is not None and index >= 0 else None
+
+
+@dataclasses.dataclass(frozen=True)
+class _ExecutionRun:
+  """What one call of compare_layer_execution gives every op: the float model, the samples, the kernels, the keywords."""
+  ref: Any
+  sg_ref: int
+  samples: list
+  kernels: LayerExecutionKernels
+  follow_input_transforms: bool
+  int16_activations: bool
+  quantized_outputs: bool
+  op_key: bool           # every entry carries `op` (a keyword of another op kind is on)
+
+
+_FLOAT_TYPES = (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16)
+_NO_TRANSFORM = (TRANSFORM_NONE, None, 0)
+
+
+# ---- what the graph says about one op: each reader returns its value, or the SKIP_* reason there is none
+def _record(out: LayerExecutionComparison, y_name: str, entry) -> None:
+  if isinstance(entry, str):
+    out.skipped[y_name] = entry
+  else:
+    out.results[y_name] = entry
+
+
+def _target_op(graph: _TargetGraph, y_name: str, builtin: int):
+  """The target op of kind `builtin` that writes `y_name` and has inputs 0 and 1, or None."""
+  op = graph.producer_op.get(y_name)
+  if op is None or graph.code(op) != builtin or len(op.inputs) < 2 or op.inputs[0] < 0 or op.inputs[1] < 0:
+    return None
+  return op
+
+
+def _target_constant(graph: _TargetGraph, op, name: str, count: int, float_reason: str = SKIP_FLOAT_TARGET):
+  """(tensor, through_dequantize) of the constant that input 1 of the target op reads: the integer constant itself, or
+  a DEQUANTIZE of it. It bears the float constant's `name`, has data and `count` elements.
+  `float_reason`: BATCH_MATMUL passes SKIP_BMM_FLOAT, the other kinds SKIP_FLOAT_TARGET."""
+  tgt, tensors = graph.tgt, graph.tgt_sg.tensors
+  target, through_dequantize = tensors[op.inputs[1]], False
+  if not _has_data(tgt.buffers, target):
+    deq = graph.producers.get(int(op.inputs[1]))
+    if not (deq is not None and graph.code(deq) == _DEQUANTIZE and len(deq.inputs) and deq.inputs[0] >= 0):
+      return SKIP_TARGET
+    target, through_dequantize = tensors[deq.inputs[0]], True
+  if schema.tensor_name(target) != name or not _has_data(tgt.buffers, target) or _numel(target) != count:
+    return SKIP_TARGET
+  if target.type in _FLOAT_TYPES:
+    return float_reason
+  return target, through_dequantize
+
+
+def _quantized_activation(graph: _TargetGraph, index: int, want_name: str, *, int16: bool, zero_point_range: bool = True):
+  """(scale, zero point, bits) of the target tensor `index`: INT8 or INT16 with one scale, `want_name` itself or a
+  QUANTIZE of it, an INT16 zero point 0 or absent.
+  `int16`: FULLY_CONNECTED and the two convolutions pass `int16_activations`; BATCH_MATMUL passes False (its kernels
+  are int8), so that an INT16 input is SKIP_INT16 whatever the keyword.
+  `zero_point_range`: whether an INT8 zero point outside [-128, 127] is refused; FULLY_CONNECTED passes False (it has
+  never checked), the other three kinds True."""
+  t = graph.tgt_sg.tensors[index]
+  if t.type == schema.TensorType.INT16 and not int16:
+    return SKIP_INT16
+  if t.type not in (schema.TensorType.INT8, schema.TensorType.INT16):
+    return SKIP_INPUT
+  q = t.quantization
+  source = graph.name(index)
+  quantize = graph.producers.get(int(index))
+  if quantize is not None and graph.code(quantize) == _QUANTIZE and len(quantize.inputs):
+    source = graph.name(quantize.inputs[0])
+  if q is None or q.scale is None or len(q.scale) != 1 or source != want_name:
+    return SKIP_INPUT
+  zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
+  bits = 16 if t.type == schema.TensorType.INT16 else 8
+  if (bits == 16 and zero_point != 0) or (zero_point_range and not -128 <= zero_point <= 127):
+    return SKIP_INPUT
+  return float(np.float32(q.scale[0])), zero_point, bits
+
+
+def _execution_mode(graph: _TargetGraph, op, x_name: str, through_dequantize: bool, *, int16: bool,
+                    zero_point_range: bool = True, transforms_d: Optional[int] = None, dequantize_first: bool = False):
+  """(mode, (scale, zero point, bits) or None, input transform) of a target op whose input 0 stands for the float
+  model's `x_name` and whose constant is read `through_dequantize` or not: a FLOAT32 input is "weight_only" behind a
+  DEQUANTIZE and "dynamic" otherwise, a quantized one (_quantized_activation, which takes `int16` and
+  `zero_point_range`) is "static" and goes with the integer constant itself.
+  `transforms_d`: the reduction dimension when an inserted op in front of a float input is followed
+  (_input_transform), None when it is not; FULLY_CONNECTED passes d under `follow_input_transforms`, the convolutions
+  and BATCH_MATMUL never follow.
+  `dequantize_first`: BATCH_MATMUL passes True, a quantized input in front of a DEQUANTIZE'd constant is SKIP_INPUT
+  before its type is looked at; for the other kinds an INT16 input without `int16_activations` is SKIP_INT16 first."""
+  index = op.inputs[0]
+  if graph.tgt_sg.tensors[index].type == schema.TensorType.FLOAT32:
+    mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
+    if graph.name(index) == x_name:
+      return mode, None, _NO_TRANSFORM
+    found = None
+    if transforms_d is not None:
+      found = _input_transform(graph.tgt, graph.tgt_sg, graph.producers, op, x_name, transforms_d)
+    return SKIP_INPUT if found is None else (mode, None, found)
+  if through_dequantize and dequantize_first:
+    return SKIP_INPUT
+  quant = _quantized_activation(graph, index, x_name, int16=int16, zero_point_range=zero_point_range)
+  if isinstance(quant, str):
+    return quant
+  return SKIP_INPUT if through_dequantize else (MODE_STATIC, quant, _NO_TRANSFORM)
+
+
+def _constant_plan(graph: _TargetGraph, ref, w, target, kinds: tuple, kind_reason: str, blockwise_reason: Optional[str],
+                   axis: Optional[tuple] = None, axis_reason: str = SKIP_TARGET, scale_count: bool = False):
+  """(the float constant's values, the ConstantPlan of the integer constant `target`) for a constant of one of
+  `kinds`, dequantized by scales, with no zero point.
+  `blockwise_reason`: None reads blockwise scales (FULLY_CONNECTED); the other kinds pass their SKIP_*_BLOCKWISE.
+  `axis`: the (channels, inner) view per-channel scales must have, None for any (FULLY_CONNECTED); its failure is
+  `axis_reason` (CONV_2D keeps SKIP_TARGET). `scale_count`: the depthwise and BATCH_MATMUL readers also want one
+  scale per channel; CONV_2D has never checked."""
+  values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(w, ref.buffers), np.float32))
+  plan = _target_plan(schema.tensor_name(w), values, graph.tgt, target)
+  if plan is None or not plan.dequantized:
+    return SKIP_TARGET
+  if plan.kind not in kinds:
+    return kind_reason
+  if plan.scale is None:
+    if blockwise_reason is not None:
+      return blockwise_reason
+    _read_blockwise_scales(plan, graph.tgt, graph.tgt_sg.tensors, target)
+  if axis is not None and (not (plan.channels == 1 or (plan.channels, plan.inner) == axis)
+                           or (scale_count and np.asarray(plan.scale).size != plan.channels)):
+    return axis_reason
+  if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
+    return SKIP_WEIGHT_ZERO_POINT
+  return values, plan
+
+
+_CONV_GEOMETRY_OPTIONS = ("padding", "stride_h", "stride_w", "dilation_h_factor", "dilation_w_factor")
+
+
+def _conv_options(reader, conv, ref_op, also: tuple = (), mismatch_reason: str = SKIP_CONV_OPTIONS):
+  """(options, strides, dilations, padding name) of a convolution whose float and target op agree about the geometry
+  and the fields `also` (else `mismatch_reason`: the depthwise op has one of its own), by `reader`."""
   from . import ops
-  from .algorithms.utils import common_utils
+  options, float_options = reader(conv), reader(ref_op)
+  if options is None or float_options is None:
+    return SKIP_CONV_OPTIONS
+  if any(options[k] != float_options[k] for k in _CONV_GEOMETRY_OPTIONS + also):
+    return mismatch_reason
+  if options["padding"] not in ops.CONV_PADDING_NAMES or min(options[k] for k in _CONV_GEOMETRY_OPTIONS[1:]) < 1:
+    return SKIP_CONV_OPTIONS
+  return (options, (options["stride_h"], options["stride_w"]), (options["dilation_h_factor"], options["dilation_w_factor"]),
+          ops.CONV_PADDING_NAMES[options["padding"]])
 
-  def code(op) -> int:
-    return int(tgt.operatorCodes[op.opcodeIndex].builtinCode)
 
-  def name(index) -> Optional[str]:
-    return schema.tensor_name(tgt_sg.tensors[index]) if index is not None and index >= 0 else None
+def _output_shapes(present: list, kernel: tuple, strides: tuple, dilations: tuple, padding: str, d: int, max_d: int):
+  """ops.conv_geometry of every sample that is not empty; SKIP_CONV_GEOMETRY when one has none or d exceeds `max_d`,
+  SKIP_NO_SAMPLE when every sample is empty."""
+  from . import ops
+  try:
+    if d > max_d:
+      raise ValueError("d")
+    shapes = [ops.conv_geometry(int(v.shape[1]), int(v.shape[2]), kernel[0], kernel[1], strides, dilations, padding)
+              for v in present if int(v.shape[0]) > 0]
+  except ValueError:
+    return SKIP_CONV_GEOMETRY
+  return shapes or SKIP_NO_SAMPLE
 
-  def int8_input(index, want_name):
-    """(scale, zero point) of the target op's INT8 input `index` that is `want_name` itself or a QUANTIZE of it; a
-    SKIP_* reason otherwise."""
-    t = tgt_sg.tensors[index]
-    if t.type == schema.TensorType.INT16:
-      return SKIP_INT16
-    if t.type != schema.TensorType.INT8:
-      return SKIP_INPUT
-    q = t.quantization
-    source = name(index)
-    quantize = producers.get(int(index))
-    if quantize is not None and code(quantize) == _QUANTIZE and len(quantize.inputs):
-      source = name(quantize.inputs[0])
-    if q is None or q.scale is None or len(q.scale) != 1 or source != want_name:
-      return SKIP_INPUT
-    zero_point = int(q.zeroPoint[0]) if q.zeroPoint is not None and len(q.zeroPoint) else 0
-    if not -128 <= zero_point <= 127:
-      return SKIP_INPUT
-    return float(np.float32(q.scale[0])), zero_point
 
-  float_types = (schema.TensorType.FLOAT32, schema.TensorType.FLOAT16, schema.TensorType.BFLOAT16)
-  for ref_op, lhs, rhs, y_name in _batch_matmul_ops(ref, sg_ref):
-    a_name, b_name = schema.tensor_name(lhs), schema.tensor_name(rhs)
-    constant = _has_data(ref.buffers, rhs)
-    if constant and (rhs.type != schema.TensorType.FLOAT32 or rhs.shape is None or len(rhs.shape) < 2):
-      out.skipped[y_name] = SKIP_BMM_RANK
-      continue
-    operands = OPERANDS_CONSTANT if constant else OPERANDS_ACTIVATIONS
-    bmm = producer_op.get(y_name)
-    if bmm is None or code(bmm) != _BATCH_MATMUL or len(bmm.inputs) < 2 or bmm.inputs[0] < 0 or bmm.inputs[1] < 0:
-      out.skipped[y_name] = SKIP_TARGET
-      continue
-    options, float_options = batch_matmul_options(bmm), batch_matmul_options(ref_op)
-    if (options is None or float_options is None
-        or any(options[k] != float_options[k] for k in ("adj_x", "adj_y"))):
-      out.skipped[y_name] = SKIP_BMM_MISMATCH
-      continue
-    adj_x, adj_y = options["adj_x"], options["adj_y"]
-    a_in = tgt_sg.tensors[bmm.inputs[0]]
-    plan, b_quant, a_quant, through_dequantize = None, None, None, False
-    if constant:
-      # ---- the constant the target op reads: the integer constant itself, or a DEQUANTIZE of it
-      read = tgt_sg.tensors[bmm.inputs[1]]
-      target = read
-      if not _has_data(tgt.buffers, read):
-        deq = producers.get(int(bmm.inputs[1]))
-        if deq is None or code(deq) != _DEQUANTIZE or not len(deq.inputs) or deq.inputs[0] < 0:
-          out.skipped[y_name] = SKIP_TARGET
-          continue
-        target, through_dequantize = tgt_sg.tensors[deq.inputs[0]], True
-      if schema.tensor_name(target) != b_name or not _has_data(tgt.buffers, target) or _numel(target) != _numel(rhs):
-        out.skipped[y_name] = SKIP_TARGET
-        continue
-      if target.type in float_types:
-        out.skipped[y_name] = SKIP_BMM_FLOAT
-        continue
-      if a_in.type == schema.TensorType.FLOAT32 and name(bmm.inputs[0]) == a_name:
-        mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
-      else:
-        a_quant = SKIP_INPUT if through_dequantize else int8_input(bmm.inputs[0], a_name)
-        if isinstance(a_quant, str):
-          out.skipped[y_name] = a_quant
-          continue
-        mode = MODE_STATIC
-      values = np.ravel(np.asarray(tfl_flatbuffer_utils.get_tensor_data(rhs, ref.buffers), np.float32))
-      plan = _target_plan(b_name, values, tgt, target)
-      if plan is None or not plan.dequantized:
-        out.skipped[y_name] = SKIP_TARGET
-        continue
-      if plan.kind != "i8":
-        out.skipped[y_name] = SKIP_BMM_KIND
-        continue
-      if plan.scale is None:
-        out.skipped[y_name] = SKIP_BMM_BLOCKWISE
-        continue
-      b_shape = [int(v) for v in rhs.shape]
-      axis = common_utils.get_bmm_weight_quantized_dim(np.empty(b_shape, np.int8), adj_y)
-      inner = int(np.prod(b_shape[axis + 1:])) if axis + 1 < len(b_shape) else 1
-      if (not (plan.channels == 1 or (plan.channels == b_shape[axis] and plan.inner == inner))
-          or np.asarray(plan.scale).size != plan.channels):
-        out.skipped[y_name] = SKIP_BMM_SCALE_AXIS
-        continue
-      if plan.zero_point is not None and np.any(np.asarray(plan.zero_point) != 0):
-        out.skipped[y_name] = SKIP_WEIGHT_ZERO_POINT
-        continue
-      if mode == MODE_DYNAMIC and adj_x:
-        out.skipped[y_name] = SKIP_BMM_DYNAMIC_ADJ_X
-        continue
-    else:
-      b_in = tgt_sg.tensors[bmm.inputs[1]]
-      if a_in.type in float_types and b_in.type in float_types:
-        out.skipped[y_name] = SKIP_BMM_FLOAT
-        continue
-      a_quant, b_quant = int8_input(bmm.inputs[0], a_name), int8_input(bmm.inputs[1], b_name)
-      bad = a_quant if isinstance(a_quant, str) else b_quant if isinstance(b_quant, str) else None
-      if bad is not None:
-        out.skipped[y_name] = bad
-        continue
-      mode = MODE_STATIC
-    # ---- the samples and their geometry
-    present = [s for s in samples if a_name in s and (constant or b_name in s)]
-    if not present:
-      out.skipped[y_name] = SKIP_NO_SAMPLE
-      continue
-    geometries = [_bmm_geometry(s[a_name].shape, rhs.shape if constant else s[b_name].shape, adj_x, adj_y) for s in present]
-    bad = next((g for g in geometries if isinstance(g, str)), None)
-    if bad is not None:
-      out.skipped[y_name] = bad
-      continue
-    d, rows = geometries[0][3], geometries[0][4]
-    if any(g[3] != d or g[4] != rows for g in geometries):
-      out.skipped[y_name] = SKIP_SAMPLE_SHAPE
-      continue
-    # ---- the output grid (static ops, `quantized_outputs`)
-    final, final_sums = None, None
-    s_b = np.asarray(plan.scale, np.float32).reshape(-1) if constant else np.array([b_quant[0]], np.float32)
-    if quantized_outputs and mode == MODE_STATIC:
-      y_t = tgt_sg.tensors[bmm.outputs[0]]
-      q = y_t.quantization
-      zp_y = int(q.zeroPoint[0]) if q is not None and q.zeroPoint is not None and len(q.zeroPoint) else 0
-      s_y = float(np.float32(q.scale[0])) if q is not None and q.scale is not None and len(q.scale) == 1 else 0.0
-      if y_t.type != schema.TensorType.INT8 or not (np.isfinite(s_y) and s_y > 0) or not -128 <= zp_y <= 127:
-        final = FINAL_SKIP_OUTPUT
-      else:
-        lo, hi = ops.QFC_SHIFT_RANGE[8]
-        try:
-          tables = [ops.quantize_multiplier(float(np.float32(a_quant[0])) * float(s) / s_y) for s in s_b.tolist()]
-          final = FINAL_SKIP_MULTIPLIER if any(not lo <= e <= hi for _, e in tables) else (
-              [m for m, _ in tables], [e for _, e in tables], s_y, zp_y)
-        except ValueError:
-          final = FINAL_SKIP_MULTIPLIER
-    if constant:
-      b_shape3 = (int(np.prod(b_shape[:-2], dtype=np.int64)), b_shape[-2], b_shape[-1])
-      b_float = kernels.weight(values, b_shape3[0] * b_shape3[1], b_shape3[2]).reshape(b_shape3)
-      t_dev = kernels.target(plan)
+# ---- the device side the three constant-weight kinds share
+def _device_operands(graph: _TargetGraph, run: _ExecutionRun, ref_op, op, values, plan, shape: tuple, rows: int, mode: str,
+                     quant, option):
+  """(float weight, integer target, dequantized weight or None, OutputPlan / FINAL_SKIP_* / None, bias, float bias) on
+  the device; `shape` is the weight's 2-D view, `option` the op kind's options reader for _output_plan."""
+  kernels = run.kernels
+  w_dev = kernels.weight(values, *shape)
+  t_dev = kernels.target(plan)
+  dq_dev = kernels.dequantized(t_dev, *shape) if mode == MODE_WEIGHT_ONLY else None
+  final, bias_dev, float_bias_dev = None, None, None
+  if run.quantized_outputs and mode == MODE_STATIC:
+    final = _output_plan(run.ref, run.ref.subgraphs[run.sg_ref], ref_op, graph.tgt, graph.tgt_sg, op, rows, quant[2],
+                         quant[0], plan.scale, option=option)
+  if isinstance(final, OutputPlan):
+    bias_dev = None if final.bias is None else kernels.bias(final.bias)
+    float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
+  return w_dev, t_dev, dq_dev, final, bias_dev, float_bias_dev
+
+
+def _quantize_static(kernels, x, quant: tuple):
+  """(q, its one scale) of `x` on the static grid `quant` = (scale, zero point, bits)."""
+  if quant[2] == 16:
+    return kernels.quantize_static16(x, quant[0])
+  return kernels.quantize_static(x, quant[0], quant[1])
+
+
+def _forward(kernels, xq, x_scale, quant: Optional[tuple], t_dev, rows: int, d: int):
+  """The integer product of quantized rows: int16 or int8 with the grid's zero point; `quant` None: dynamic rows."""
+  if quant is not None and quant[2] == 16:
+    return kernels.forward16(xq, x_scale, t_dev, rows, d)
+  return kernels.forward(xq, x_scale, 0 if quant is None else quant[1], t_dev, rows, d)
+
+
+def _stored_output(kernels, final: OutputPlan, xq, x_zero_point: int, t_dev, rows: int, d: int, bias_dev):
+  """What the static op stores for the rows `xq` (FULLY_CONNECTED, and CONV_2D on patch rows)."""
+  if final.bits == 16:
+    return kernels.output16(xq, t_dev, rows, d, bias_dev, final.multiplier, final.shift, final.act_min, final.act_max)
+  return kernels.output(xq, x_zero_point, t_dev, rows, d, bias_dev, final.multiplier, final.shift, final.zero_point,
+                        final.act_min, final.act_max)
+
+
+def _final_sqdiff(kernels, final: OutputPlan, q_out, y, float_bias_dev, final_sums):
+  """`final_sums` with the stored output `q_out`, dequantized, against the float op's act(y + b)."""
+  return kernels.sqdiff(kernels.dequantize_output(q_out, final.scale, final.zero_point),
+                        kernels.reference_output(y, float_bias_dev, final.float_fused), final_sums)
+
+
+# ---- an entry's figures
+def _error_figures(kernels, sums, tokens: int, rows: int, prefix: str = "") -> dict:
+  """signal, error, output_mse, output_snr and per_channel_error (each with `prefix`) of the sums over `tokens` rows."""
+  sq_diff, sq_ref = kernels.host(sums)
+  per_channel = np.asarray(sq_diff, np.float64) / tokens
+  signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
+  mse = error / rows
+  return {prefix + "signal": signal, prefix + "error": error, prefix + "output_mse": mse,
+          prefix + "output_snr": (signal / rows) / (mse + 1e-9), prefix + "per_channel_error": per_channel}
+
+
+def _finish_entry(entry: dict, run: _ExecutionRun, mode: str, activation_bits: Optional[int], transform: tuple, final,
+                  final_sums, tokens: int, rows: int) -> dict:
+  """The keys an entry carries by the keywords: `input_transform` / `hadamard_size`, `activation_bits`, and
+  `output_bits` with the final_* figures of an OutputPlan `final`, or `final_skipped` with the reason `final`."""
+  if run.follow_input_transforms:
+    entry.update(input_transform=transform[0], hadamard_size=transform[2])
+  if run.int16_activations:
+    entry["activation_bits"] = activation_bits
+  if run.quantized_outputs:
+    entry["output_bits"] = activation_bits if mode == MODE_STATIC else None
+    if isinstance(final, OutputPlan):
+      from . import ops
+      entry["fused_activation"] = ops.FUSED_ACTIVATION_NAMES[final.fused]
+      entry.update(_error_figures(run.kernels, final_sums, tokens, rows, "final_"))
+    elif final is not None:
+      entry["final_skipped"] = final
+  return entry
+
+
+# ---- the four op kinds: each *_entry returns the op's entry, or the reason it has none
+def _fully_connected_entries(out, graph: _TargetGraph, run: _ExecutionRun) -> None:
+  for ref_op, x_name, w, y_name in _fully_connected_ops(run.ref, run.sg_ref):
+    _record(out, y_name, _fully_connected_entry(graph, run, ref_op, x_name, w, y_name))
+
+
+def _fully_connected_entry(graph: _TargetGraph, run: _ExecutionRun, ref_op, x_name: str, w, y_name: str):
+  kernels, ref = run.kernels, run.ref
+  if w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 2:
+    return SKIP_WEIGHT
+  rows, d = int(w.shape[0]), int(w.shape[1])
+  fc = _target_op(graph, y_name, _FULLY_CONNECTED)
+  if fc is None:
+    return SKIP_TARGET
+  found = _target_constant(graph, fc, schema.tensor_name(w), rows * d)
+  if isinstance(found, str):
+    return found
+  target, through_dequantize = found
+  found = _execution_mode(graph, fc, x_name, through_dequantize, int16=run.int16_activations, zero_point_range=False,
+                          transforms_d=d if run.follow_input_transforms else None)
+  if isinstance(found, str):
+    return found
+  mode, quant, transform = found
+  found = _constant_plan(graph, ref, w, target, ("i8", "i4", "i2"), SKIP_KIND, None)
+  if isinstance(found, str):
+    return found
+  values, plan = found
+  present = [s[x_name] for s in run.samples if x_name in s]
+  if not present:
+    return SKIP_NO_SAMPLE
+  if any(int(np.prod(v.shape)) % d for v in present):
+    return SKIP_SAMPLE_SHAPE
+  w_dev, t_dev, dq_dev, final, bias_dev, float_bias_dev = _device_operands(
+      graph, run, ref_op, fc, values, plan, (rows, d), rows, mode, quant, _fc_option)
+  sums, final_sums, tokens = None, None, 0
+  for value in present:
+    x = kernels.sample(value, d)
+    n = int(x.shape[0])
+    for first in range(0, n, EXECUTION_CHUNK_ROWS):
+      xc = kernels.rows(x, first, min(EXECUTION_CHUNK_ROWS, n - first))
+      y = kernels.gemm(xc, w_dev)
+      xt = xc if transform[0] == TRANSFORM_NONE else kernels.transform(xc, *transform)
       if mode == MODE_WEIGHT_ONLY:
-        b_deq = kernels.dequantized(t_dev, b_shape3[0] * b_shape3[1], b_shape3[2]).reshape(b_shape3)
+        yq = kernels.gemm(xt, dq_dev)
       else:
-        bq, b_scale = kernels.bmm_constant(plan, b_shape3)
-    sums, tokens = None, 0
-    for s, (batch, b_batch, m, _, _) in zip(present, geometries):
-      if batch * m == 0:
-        continue
-      a = kernels.sample_nd(s[a_name])
-      a3 = a.reshape((batch,) + tuple(a.shape[-2:]))
-      if not constant:
-        b_act = kernels.sample_nd(s[b_name])
-        b_float = b_act.reshape((b_batch,) + tuple(b_act.shape[-2:]))
-      # the sample is quantized ONCE, as the op sees it
-      if mode == MODE_STATIC:
-        aq, a_scale = kernels.quantize_static(a3, *a_quant)
-        if not constant:
-          bq, b_scale = kernels.quantize_static(b_float, *b_quant)
-        zps = (a_quant[1], 0 if constant else b_quant[1])
-        yq = kernels.bmm_forward(aq, bq, adj_x, adj_y, a_scale, zps[0], b_scale, zps[1])
-        if isinstance(final, tuple):
-          q_out = kernels.bmm_output(aq, bq, adj_x, adj_y, zps[0], zps[1], final[0], final[1], final[3])
-          y_final = kernels.dequantize_output(q_out, final[2], final[3])
-      elif mode == MODE_DYNAMIC:
-        aq, a_scale = kernels.quantize_dynamic(a3.reshape(batch * m, d))
-        yq = kernels.bmm_forward(aq.reshape(batch, m, d), bq, adj_x, adj_y, a_scale, 0, b_scale, 0)
-      for i in range(batch):
-        j = i if b_batch != 1 else 0
-        y = kernels.bmm_float(a3[i], b_float[j], adj_x, adj_y)
-        yq_i = kernels.bmm_float(a3[i], b_deq[j], adj_x, adj_y) if mode == MODE_WEIGHT_ONLY else yq[i]
-        for first in range(0, m, EXECUTION_CHUNK_ROWS):
-          count = min(EXECUTION_CHUNK_ROWS, m - first)
-          y_c = kernels.rows(y, first, count)
-          sums = kernels.sqdiff(kernels.rows(yq_i, first, count), y_c, sums)
-          if isinstance(final, tuple):
-            final_sums = kernels.sqdiff(kernels.rows(y_final[i], first, count), y_c, final_sums)
-      tokens += batch * m
-    if sums is None:          # (every sample was empty)
-      out.skipped[y_name] = SKIP_NO_SAMPLE
+        xq, x_scale = kernels.quantize_dynamic(xt) if mode == MODE_DYNAMIC else _quantize_static(kernels, xt, quant)
+        yq = _forward(kernels, xq, x_scale, quant, t_dev, rows, d)
+      sums = kernels.sqdiff(yq, y, sums)
+      if isinstance(final, OutputPlan):
+        q_out = _stored_output(kernels, final, xq, quant[1], t_dev, rows, d, bias_dev)
+        final_sums = _final_sqdiff(kernels, final, q_out, y, float_bias_dev, final_sums)
+    tokens += n
+  if sums is None:          # (every sample of the input was empty)
+    return SKIP_NO_SAMPLE
+  entry = {"weight": schema.tensor_name(w), "input": x_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
+           **_error_figures(kernels, sums, tokens, rows)}
+  _finish_entry(entry, run, mode, quant and quant[2], transform, final, final_sums, tokens, rows)
+  if run.op_key:
+    entry["op"] = "FULLY_CONNECTED"
+  return entry
+
+
+def _conv_2d_entries(out, graph: _TargetGraph, run: _ExecutionRun) -> None:
+  """CONV_2D: the same product on patch rows (compare_layer_execution's section on `conv_2d`)."""
+  for ref_op, x_name, w, y_name in _conv_2d_ops(run.ref, run.sg_ref):
+    _record(out, y_name, _conv_2d_entry(graph, run, ref_op, x_name, w, y_name))
+
+
+def _conv_2d_entry(graph: _TargetGraph, run: _ExecutionRun, ref_op, x_name: str, w, y_name: str):
+  from . import ops
+  kernels, ref = run.kernels, run.ref
+  if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
+      or min(int(v) for v in w.shape) < 1):
+    return SKIP_CONV_FILTER
+  rows, kh, kw, channels = (int(v) for v in w.shape)
+  d = kh * kw * channels
+  conv = _target_op(graph, y_name, _CONV_2D)
+  if conv is None:
+    return SKIP_TARGET
+  found = _conv_options(conv_2d_options, conv, ref_op)
+  if isinstance(found, str):
+    return found
+  _, strides, dilations, padding = found
+  found = _target_constant(graph, conv, schema.tensor_name(w), rows * d)
+  if isinstance(found, str):
+    return found
+  target, through_dequantize = found
+  found = _execution_mode(graph, conv, x_name, through_dequantize, int16=run.int16_activations)
+  if isinstance(found, str):
+    return found
+  mode, quant, transform = found
+  # the filter as a [O, K] constant: K = KH KW I is contiguous per output channel (scales along dimension 0)
+  found = _constant_plan(graph, ref, w, target, ("i8", "i4", "i2"), SKIP_KIND, SKIP_CONV_BLOCKWISE, axis=(rows, d))
+  if isinstance(found, str):
+    return found
+  values, plan = found
+  present = [s[x_name] for s in run.samples if x_name in s]
+  if not present:
+    return SKIP_NO_SAMPLE
+  if any(len(v.shape) != 4 for v in present):
+    return SKIP_SAMPLE_SHAPE
+  if any(int(v.shape[3]) != channels for v in present):
+    return SKIP_CONV_GROUPS
+  shapes = _output_shapes(present, (kh, kw), strides, dilations, padding, d, ops.QFC_MAX_D)
+  if isinstance(shapes, str):
+    return shapes
+  w_dev, t_dev, dq_dev, final, bias_dev, float_bias_dev = _device_operands(
+      graph, run, ref_op, conv, values, plan, (rows, d), rows, mode, quant, _conv_option)
+  sums, final_sums, tokens = None, None, 0
+  gather = (kh, kw), strides, dilations, padding
+  for value in present:
+    if int(value.shape[0]) == 0:
       continue
-    sq_diff, sq_ref = kernels.host(sums)
-    per_channel = np.asarray(sq_diff, np.float64) / tokens
-    signal, error = float(np.sum(np.asarray(sq_ref, np.float64)) / tokens), float(np.sum(sq_diff) / tokens)
-    mse = error / rows
-    entry = out.results[y_name] = {
-        "op": "BATCH_MATMUL", "operands": operands, "adj_x": adj_x, "adj_y": adj_y, "batch": geometries[0][0],
-        "weight": b_name if constant else None, "input": a_name, "rows": rows, "d": d, "tokens": tokens, "mode": mode,
-        "signal": signal, "error": error, "output_mse": mse, "output_snr": (signal / rows) / (mse + 1e-9),
-        "per_channel_error": per_channel, "activation_bits": 8 if mode == MODE_STATIC else None}
+    x = kernels.sample4d(value)
+    oh, ow, _, _ = ops.conv_geometry(int(x.shape[1]), int(x.shape[2]), kh, kw, strides, dilations, padding)
+    n = int(x.shape[0]) * oh * ow
+    # the whole sample is quantized ONCE and the patches are gathered from the integer tensor, padded with the zero
+    # point: q(0.0) = zp_x, so these are the bits of quantizing float patches padded with 0.0
+    if mode == MODE_DYNAMIC:
+      xq_all, scale_rows = kernels.quantize_dynamic_images(x, oh * ow)
+    elif mode == MODE_STATIC:
+      xq_all, x_scale = _quantize_static(kernels, x, quant)
+    pad = quant[1] if mode == MODE_STATIC and quant[2] == 8 else 0
+    for first in range(0, n, EXECUTION_CHUNK_ROWS):
+      count = min(EXECUTION_CHUNK_ROWS, n - first)
+      xc = kernels.patches(x, *gather, 0.0, first, count)
+      y = kernels.gemm(xc, w_dev)
+      if mode == MODE_WEIGHT_ONLY:
+        yq = kernels.gemm(xc, dq_dev)
+      else:
+        xq = kernels.patches(xq_all, *gather, pad, first, count)
+        yq = _forward(kernels, xq, kernels.rows(scale_rows, first, count) if mode == MODE_DYNAMIC else x_scale, quant,
+                      t_dev, rows, d)
+      sums = kernels.sqdiff(yq, y, sums)
+      if isinstance(final, OutputPlan):
+        q_out = _stored_output(kernels, final, xq, quant[1], t_dev, rows, d, bias_dev)
+        final_sums = _final_sqdiff(kernels, final, q_out, y, float_bias_dev, final_sums)
+    tokens += n
+  entry = {"op": "CONV_2D", "weight": schema.tensor_name(w), "input": x_name, "rows": rows, "d": d, "tokens": tokens,
+           "mode": mode, "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations), "padding": padding,
+           "output_hw": [shapes[0][0], shapes[0][1]], **_error_figures(kernels, sums, tokens, rows)}
+  return _finish_entry(entry, run, mode, quant and quant[2], transform, final, final_sums, tokens, rows)
+
+
+def _depthwise_conv_2d_entries(out, graph: _TargetGraph, run: _ExecutionRun) -> None:
+  """DEPTHWISE_CONV_2D: a direct convolution, no patch rows (compare_layer_execution's section on
+  `depthwise_conv_2d`)."""
+  for ref_op, x_name, w, y_name in _depthwise_conv_2d_ops(run.ref, run.sg_ref):
+    _record(out, y_name, _depthwise_conv_2d_entry(graph, run, ref_op, x_name, w, y_name))
+
+
+def _depthwise_conv_2d_entry(graph: _TargetGraph, run: _ExecutionRun, ref_op, x_name: str, w, y_name: str):
+  from . import ops
+  kernels, ref = run.kernels, run.ref
+  if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
+      or int(w.shape[0]) != 1 or min(int(v) for v in w.shape) < 1):
+    return SKIP_DEPTHWISE_FILTER
+  _, kh, kw, rows = (int(v) for v in w.shape)
+  d = kh * kw
+  conv = _target_op(graph, y_name, _DEPTHWISE_CONV_2D)
+  if conv is None:
+    return SKIP_TARGET
+  found = _conv_options(depthwise_conv_2d_options, conv, ref_op, ("depth_multiplier",), SKIP_DEPTHWISE_MISMATCH)
+  if isinstance(found, str):
+    return found
+  options, strides, dilations, padding = found
+  found = _target_constant(graph, conv, schema.tensor_name(w), rows * d)
+  if isinstance(found, str):
+    return found
+  target, through_dequantize = found
+  found = _execution_mode(graph, conv, x_name, through_dequantize, int16=run.int16_activations)
+  if isinstance(found, str):
+    return found
+  mode, quant, transform = found
+  # the filter as a [KH KW, O] constant, the stored bytes of [1, KH, KW, O]: scales along dimension 3 (O scales along
+  # dimension 0, of size 1, are read as one and refused by their count)
+  found = _constant_plan(graph, ref, w, target, ("i8",), SKIP_DEPTHWISE_KIND, SKIP_DEPTHWISE_BLOCKWISE, axis=(rows, 1),
+                         axis_reason=SKIP_DEPTHWISE_SCALE_AXIS, scale_count=True)
+  if isinstance(found, str):
+    return found
+  values, plan = found
+  present = [s[x_name] for s in run.samples if x_name in s]
+  if not present:
+    return SKIP_NO_SAMPLE
+  if any(len(v.shape) != 4 for v in present):
+    return SKIP_SAMPLE_SHAPE
+  channels = int(present[0].shape[3])
+  if (channels < 1 or any(int(v.shape[3]) != channels for v in present) or rows % channels
+      or options["depth_multiplier"] not in (0, rows // channels)):
+    return SKIP_DEPTHWISE_MULTIPLIER
+  multiplier = rows // channels
+  shapes = _output_shapes(present, (kh, kw), strides, dilations, padding, d, ops.DWCONV_MAX_TAPS)
+  if isinstance(shapes, str):
+    return shapes
+  w_dev, t_dev, dq_dev, final, bias_dev, float_bias_dev = _device_operands(
+      graph, run, ref_op, conv, values, plan, (d, rows), rows, mode, quant, _depthwise_option)
+  sums, final_sums, tokens = None, None, 0
+  where = (kh, kw), multiplier, strides, dilations, padding
+  for value in present:
+    if int(value.shape[0]) == 0:
+      continue
+    x = kernels.sample4d(value)
+    oh, ow, _, _ = ops.conv_geometry(int(x.shape[1]), int(x.shape[2]), kh, kw, strides, dilations, padding)
+    n = int(x.shape[0]) * oh * ow
+    # the sample is quantized ONCE; a tap outside the image is skipped, which is what a pad element q(0.0) = zp_x adds
+    if mode == MODE_DYNAMIC:
+      xq_all, x_scale = kernels.quantize_dynamic_images(x, 1)      # (one scale per image)
+    elif mode == MODE_STATIC:
+      xq_all, x_scale = _quantize_static(kernels, x, quant)
+    for first in range(0, n, EXECUTION_CHUNK_ROWS):
+      count = min(EXECUTION_CHUNK_ROWS, n - first)
+      y = kernels.depthwise_float(x, w_dev, *where, first, count)
+      if mode == MODE_WEIGHT_ONLY:
+        yq = kernels.depthwise_float(x, dq_dev, *where, first, count)
+      elif mode == MODE_STATIC and quant[2] == 16:
+        yq = kernels.depthwise_forward16(xq_all, x_scale, t_dev, *where, first, count)
+      else:
+        yq = kernels.depthwise_forward(xq_all, x_scale, 0 if mode == MODE_DYNAMIC else quant[1], t_dev, *where, first, count)
+      sums = kernels.sqdiff(yq, y, sums)
+      # (the four depthwise calls stay here: sharing _stored_output would take a table of callables)
+      if isinstance(final, OutputPlan):
+        if final.bits == 16:
+          q_out = kernels.depthwise_output16(xq_all, t_dev, *where, bias_dev, final.multiplier, final.shift, final.act_min,
+                                             final.act_max, first, count)
+        else:
+          q_out = kernels.depthwise_output(xq_all, quant[1], t_dev, *where, bias_dev, final.multiplier, final.shift,
+                                           final.zero_point, final.act_min, final.act_max, first, count)
+        final_sums = _final_sqdiff(kernels, final, q_out, y, float_bias_dev, final_sums)
+    tokens += n
+  entry = {"op": "DEPTHWISE_CONV_2D", "weight": schema.tensor_name(w), "input": x_name, "rows": rows, "d": d,
+           "tokens": tokens, "mode": mode, "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations),
+           "padding": padding, "output_hw": [shapes[0][0], shapes[0][1]], "depth_multiplier": multiplier,
+           **_error_figures(kernels, sums, tokens, rows)}
+  return _finish_entry(entry, run, mode, quant and quant[2], transform, final, final_sums, tokens, rows)
+
+
+def _batch_matmul_entries(out, graph: _TargetGraph, run: _ExecutionRun) -> None:
+  """BATCH_MATMUL: the integer batched product (compare_layer_execution's section on `batch_matmul`)."""
+  for ref_op, lhs, rhs, y_name in _batch_matmul_ops(run.ref, run.sg_ref):
+    _record(out, y_name, _batch_matmul_entry(graph, run, ref_op, lhs, rhs, y_name))
+
+
+def _bmm_output_plan(y, s_a: float, s_b: np.ndarray):
+  """The OutputPlan of a static BATCH_MATMUL with the output tensor `y` (the op has neither bias nor fused
+  activation), or the FINAL_SKIP_* reason there is none."""
+  from . import ops
+  grid = _output_grid(y, 8)
+  if isinstance(grid, str):
+    return grid
+  table = _multiplier_table(s_a, s_b, grid[0], 8)
+  if isinstance(table, str):
+    return table
+  act_min, act_max = ops.activation_range(ops.FUSED_NONE, grid[0], grid[1], 8)
+  return OutputPlan(8, None, None, table[0], table[1], grid[0], grid[1], act_min, act_max, ops.FUSED_NONE, ops.FUSED_NONE)
+
+
+def _batch_matmul_entry(graph: _TargetGraph, run: _ExecutionRun, ref_op, lhs, rhs, y_name: str):
+  from .algorithms.utils import common_utils
+  kernels, ref, tensors = run.kernels, run.ref, graph.tgt_sg.tensors
+  a_name, b_name = schema.tensor_name(lhs), schema.tensor_name(rhs)
+  constant = _has_data(ref.buffers, rhs)
+  if constant and (rhs.type != schema.TensorType.FLOAT32 or rhs.shape is None or len(rhs.shape) < 2):
+    return SKIP_BMM_RANK
+  bmm = _target_op(graph, y_name, _BATCH_MATMUL)
+  if bmm is None:
+    return SKIP_TARGET
+  options, float_options = batch_matmul_options(bmm), batch_matmul_options(ref_op)
+  if options is None or float_options is None or any(options[k] != float_options[k] for k in ("adj_x", "adj_y")):
+    return SKIP_BMM_MISMATCH
+  adj_x, adj_y = options["adj_x"], options["adj_y"]
+  b_quant = None
+  if constant:
+    found = _target_constant(graph, bmm, b_name, _numel(rhs), float_reason=SKIP_BMM_FLOAT)
+    if isinstance(found, str):
+      return found
+    target, through_dequantize = found
+    found = _execution_mode(graph, bmm, a_name, through_dequantize, int16=False, dequantize_first=True)
+    if isinstance(found, str):
+      return found
+    mode, a_quant, _ = found
+    # an int8 constant with scales per tensor or along its output axis
+    b_shape = [int(v) for v in rhs.shape]
+    axis = common_utils.get_bmm_weight_quantized_dim(np.empty(b_shape, np.int8), adj_y)
+    inner = int(np.prod(b_shape[axis + 1:])) if axis + 1 < len(b_shape) else 1
+    found = _constant_plan(graph, ref, rhs, target, ("i8",), SKIP_BMM_KIND, SKIP_BMM_BLOCKWISE, axis=(b_shape[axis], inner),
+                           axis_reason=SKIP_BMM_SCALE_AXIS, scale_count=True)
+    if isinstance(found, str):
+      return found
+    values, plan = found
+    if mode == MODE_DYNAMIC and adj_x:
+      return SKIP_BMM_DYNAMIC_ADJ_X
+  else:
+    if tensors[bmm.inputs[0]].type in _FLOAT_TYPES and tensors[bmm.inputs[1]].type in _FLOAT_TYPES:
+      return SKIP_BMM_FLOAT
+    a_quant = _quantized_activation(graph, bmm.inputs[0], a_name, int16=False)
+    b_quant = _quantized_activation(graph, bmm.inputs[1], b_name, int16=False)
+    bad = a_quant if isinstance(a_quant, str) else b_quant if isinstance(b_quant, str) else None
+    if bad is not None:
+      return bad
+    mode = MODE_STATIC
+  # ---- the samples and their geometry
+  present = [s for s in run.samples if a_name in s and (constant or b_name in s)]
+  if not present:
+    return SKIP_NO_SAMPLE
+  geometries = [_bmm_geometry(s[a_name].shape, rhs.shape if constant else s[b_name].shape, adj_x, adj_y) for s in present]
+  bad = next((g for g in geometries if isinstance(g, str)), None)
+  if bad is not None:
+    return bad
+  d, rows = geometries[0][3], geometries[0][4]
+  if any(g[3] != d or g[4] != rows for g in geometries):
+    return SKIP_SAMPLE_SHAPE
+  # ---- the output grid (static ops, `quantized_outputs`)
+  final, final_sums = None, None
+  if run.quantized_outputs and mode == MODE_STATIC:
+    s_b = np.asarray(plan.scale, np.float32).reshape(-1) if constant else np.array([b_quant[0]], np.float32)
+    final = _bmm_output_plan(tensors[bmm.outputs[0]], a_quant[0], s_b)
+  if constant:
+    b_shape3 = (int(np.prod(b_shape[:-2], dtype=np.int64)), b_shape[-2], b_shape[-1])
+    b_float = kernels.weight(values, b_shape3[0] * b_shape3[1], b_shape3[2]).reshape(b_shape3)
+    t_dev = kernels.target(plan)
+    if mode == MODE_WEIGHT_ONLY:
+      b_deq = kernels.dequantized(t_dev, b_shape3[0] * b_shape3[1], b_shape3[2]).reshape(b_shape3)
+    else:
+      bq, b_scale = kernels.bmm_constant(plan, b_shape3)
+  sums, tokens = None, 0
+  for s, (batch, b_batch, m, _, _) in zip(present, geometries):
+    if batch * m == 0:
+      continue
+    a = kernels.sample_nd(s[a_name])
+    a3 = a.reshape((batch,) + tuple(a.shape[-2:]))
     if not constant:
-      entry["input_b"] = b_name
-    if follow_input_transforms:
-      entry.update(input_transform=TRANSFORM_NONE, hadamard_size=0)
-    if quantized_outputs:
-      entry["output_bits"] = 8 if mode == MODE_STATIC else None
-      if isinstance(final, tuple):
-        f_diff, f_ref = kernels.host(final_sums)
-        f_channel = np.asarray(f_diff, np.float64) / tokens
-        f_signal, f_error = float(np.sum(np.asarray(f_ref, np.float64)) / tokens), float(np.sum(f_diff) / tokens)
-        f_mse = f_error / rows
-        entry.update(fused_activation="NONE", final_signal=f_signal, final_error=f_error, final_output_mse=f_mse,
-                     final_output_snr=(f_signal / rows) / (f_mse + 1e-9), final_per_channel_error=f_channel)
-      elif final is not None:
-        entry["final_skipped"] = final
+      b_act = kernels.sample_nd(s[b_name])
+      b_float = b_act.reshape((b_batch,) + tuple(b_act.shape[-2:]))
+    # the sample is quantized ONCE, as the op sees it
+    if mode == MODE_STATIC:
+      aq, a_scale = kernels.quantize_static(a3, a_quant[0], a_quant[1])
+      if not constant:
+        bq, b_scale = kernels.quantize_static(b_float, b_quant[0], b_quant[1])
+      zps = (a_quant[1], 0 if constant else b_quant[1])
+      yq = kernels.bmm_forward(aq, bq, adj_x, adj_y, a_scale, zps[0], b_scale, zps[1])
+      if isinstance(final, OutputPlan):
+        q_out = kernels.bmm_output(aq, bq, adj_x, adj_y, zps[0], zps[1], final.multiplier, final.shift, final.zero_point)
+        y_final = kernels.dequantize_output(q_out, final.scale, final.zero_point)
+    elif mode == MODE_DYNAMIC:
+      aq, a_scale = kernels.quantize_dynamic(a3.reshape(batch * m, d))
+      yq = kernels.bmm_forward(aq.reshape(batch, m, d), bq, adj_x, adj_y, a_scale, 0, b_scale, 0)
+    for i in range(batch):
+      j = i if b_batch != 1 else 0
+      y = kernels.bmm_float(a3[i], b_float[j], adj_x, adj_y)
+      yq_i = kernels.bmm_float(a3[i], b_deq[j], adj_x, adj_y) if mode == MODE_WEIGHT_ONLY else yq[i]
+      for first in range(0, m, EXECUTION_CHUNK_ROWS):
+        count = min(EXECUTION_CHUNK_ROWS, m - first)
+        y_c = kernels.rows(y, first, count)
+        sums = kernels.sqdiff(kernels.rows(yq_i, first, count), y_c, sums)
+        if isinstance(final, OutputPlan):
+          final_sums = kernels.sqdiff(kernels.rows(y_final[i], first, count), y_c, final_sums)
+    tokens += batch * m
+  if sums is None:          # (every sample was empty)
+    return SKIP_NO_SAMPLE
+  activation_bits = 8 if mode == MODE_STATIC else None
+  entry = {"op": "BATCH_MATMUL", "operands": OPERANDS_CONSTANT if constant else OPERANDS_ACTIVATIONS, "adj_x": adj_x,
+           "adj_y": adj_y, "batch": geometries[0][0], "weight": b_name if constant else None, "input": a_name, "rows": rows,
+           "d": d, "tokens": tokens, "mode": mode, **_error_figures(kernels, sums, tokens, rows),
+           "activation_bits": activation_bits}
+  if not constant:
+    entry["input_b"] = b_name
+  return _finish_entry(entry, run, mode, activation_bits, _NO_TRANSFORM, final, final_sums, tokens, rows)
 
 
 # ----------------------------------------------------------------------------- sensitivity sweep
