@@ -1,4 +1,4 @@
-"""Inputs and expected values for the three entry points of the MSE scale (a14, csrc/reduce_exact.hip):
+"""Inputs and expected values for the three entry points of the MSE scale (a14, csrc/mse_scale.hip):
 
   mi355q_mse_scale_f32      mse_scale_balanced_kernel | mse_scale_leaves_kernel
   mi355q_mse_scale_nd_f32   outer == 1: the entry above; channels == 1: the entry above on one unit of outer * inner

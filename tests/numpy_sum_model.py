@@ -1,6 +1,6 @@
 """Pure-Python model of the order in which NumPy adds float32 values in
 np.sum(x, axis, where=mask) / np.sum(x, axis) -- the order libmi355q's
-reduce_exact.hip reproduces on the GPU. test_numpy_sum_model.py proves the
+numpy_sum.h and the kernels built on it reproduce on the GPU. test_numpy_sum_model.py proves the
 model against NumPy itself."""
 import numpy as np
 

@@ -1,4 +1,4 @@
-"""Cases for every route of the OCTAV clip search (csrc/reduce_exact.hip: mi355q_octav_clip_f32, _fast_f32, _nd_f32),
+"""Cases for every route of the OCTAV clip search (csrc/octav.hip: mi355q_octav_clip_f32, _fast_f32, _nd_f32),
 shared by test_octav_route_cases_host.py (no GPU) and test_gpu_octav_routes.py.
 
 Three restatements, none of which needs a GPU:
@@ -234,7 +234,7 @@ def iterates(x, bits, max_iter, count_is_f64=1, axes=(1,)):
 
 
 def step_next(pos_sum, neg_sum, count_pos, count_neg, n, bits, count_is_f64):
-  """octav_step of reduce_exact.hip in NumPy scalars: the next iterate from the two masked sums and their counts."""
+  """octav_step of octav_common.h in NumPy scalars: the next iterate from the two masked sums and their counts."""
   s = F(4.0 ** (-bits) / DIVISOR)
   with np.errstate(all="ignore"):
     num = F(F(pos_sum) - F(neg_sum))

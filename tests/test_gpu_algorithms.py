@@ -393,7 +393,7 @@ def test_octav_masked_sums_with_designed_run_lengths(m, seed):
 @pytest.mark.parametrize("block", [32, 64, 128, 256, 512])
 def test_octav_blockwise_groups_kernel_bit_exact(m, block):
   """Blockwise units on a tensor that is a whole number of 4096-element groups. By the dispatch of
-  mi355q_octav_clip_f32 (csrc/reduce_exact.hip) blocks of 32 / 64 / 128 / 256 take the lane-per-unit
+  mi355q_octav_clip_f32 (csrc/octav.hip) blocks of 32 / 64 / 128 / 256 take the lane-per-unit
   kernel here (octav_groups_kernel -- 4096 contiguous elements = 32 .. 128 whole units per workgroup --
   only with MI355Q_OCTAV_UNIT_LANES=0, and then not for 256), and blocks of 256 without that kernel
   and of 512 take the rows kernel, as every unit of 129 .. 16384 elements does (the name is from

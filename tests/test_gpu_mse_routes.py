@@ -1,5 +1,5 @@
 """Every route of the MSE scale kernels (mi355q_mse_scale_f32, mi355q_mse_scale_nd_f32, mi355q_mse_requant_f32;
-csrc/reduce_exact.hip), bit for bit against the reference's NumPy expressions.
+csrc/mse_scale.hip), bit for bit against the reference's NumPy expressions.
 
 The cases, their expected values, the restatement of the host's choice of kernels and the proof that each case shows
 the defects its route could have are in mse_route_cases.py / test_mse_route_cases_host.py, which need no GPU. Here the

@@ -1,4 +1,4 @@
-"""Every route of the OCTAV clip search (csrc/reduce_exact.hip: mi355q_octav_clip_f32, mi355q_octav_clip_fast_f32,
+"""Every route of the OCTAV clip search (csrc/octav.hip: mi355q_octav_clip_f32, mi355q_octav_clip_fast_f32,
 mi355q_octav_clip_nd_f32), iterate by iterate and bit for bit against NumPy.
 
 OCTAV is a fixed-point iteration: once the masks settle, the last masks alone determine the result, and an early iterate

@@ -1,4 +1,4 @@
-"""OCTAV on blockwise units of 32 / 64 / 128 / 256 elements: the lane-per-unit kernel (csrc/reduce_exact.hip,
+"""OCTAV on blockwise units of 32 / 64 / 128 / 256 elements: the lane-per-unit kernel (csrc/octav_unit_lanes.hip,
 octav_unit_lanes_kernel) against the oracle's NumPy iteration (ref octav.py:30-112) and against the kernel it replaced
 (MI355Q_OCTAV_UNIT_LANES=0: octav_groups_kernel; the rows kernel for units of 256), bit for bit: clipping constants AND iteration counts.
 

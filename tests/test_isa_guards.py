@@ -45,7 +45,7 @@ def _assembly(name: str, out_dir: str) -> str:
 @pytest.fixture(scope="module")
 def asm(tmp_path_factory):
   out_dir = str(tmp_path_factory.mktemp("isa"))
-  names = ("gemm", "xtx_bf16x3", "xtx_f16x2", "reduce_exact")
+  names = ("gemm", "xtx_bf16x3", "xtx_f16x2", "octav_unit_lanes")
   with concurrent.futures.ThreadPoolExecutor(len(names)) as pool:
     return dict(zip(names, pool.map(lambda n: _assembly(n, out_dir), names)))
 
@@ -136,7 +136,7 @@ def test_ring_kernels_keep_their_pieces_in_flight_across_the_barrier(asm):
 
 
 def test_octav_unit_lanes_kernel_keeps_its_unit_in_registers_and_its_fast_step_off_the_scalar_file(asm):
-  kernels = {n: b for n, b in _kernels(asm["reduce_exact"]).items() if "octav_unit_lanes_kernel" in n}
+  kernels = {n: b for n, b in _kernels(asm["octav_unit_lanes"]).items() if "octav_unit_lanes_kernel" in n}
   assert len(kernels) == 4                       # units of 32 / 64 / 128 / 256
   for name, body in kernels.items():
     wide = "ILi256E" in name      # (sixteen tuples + the walks' state: a few values of the set-up code go to scratch; never the walks)

@@ -1,7 +1,7 @@
 """What tests/test_gpu_mse_routes.py holds the MSE scale kernels to, proved without a GPU (mse_route_cases.py):
 
   1. the reference's NumPy expressions equal the in-order models on every case, bit for bit -- so the orders
-     reduce_exact.hip reproduces (8192-element chunks, pairwise with splits at multiples of 8, eight accumulators and a
+     mse_scale.hip reproduces (8192-element chunks, pairwise with splits at multiples of 8, eight accumulators and a
      tail, row by row, segment by segment, one vector for one channel) are NumPy's;
   2. route() over the case list reaches every element of REQUIRED, agrees with balanced_chunk restated from common.h at
      every length up to three chunks and a leaf, and the lengths the kernels' code singles out land where stated;

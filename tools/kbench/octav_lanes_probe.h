@@ -1,10 +1,10 @@
 // OCTAV on weight rows, round 4: rows in registers, run totals through LDS, the serial chains of a
-// workgroup's rows on the LANES of one wave.   (included by reduce_exact.hip, inside its namespace)
+// workgroup's rows on the LANES of one wave.   (it compiled inside octav_rows.hip, in its namespace)
 //
 //   ref: algorithms/uniform_quantize/octav.py:30-112 (_guess_clipping_with_octav)
 //
 // What the reference fixes: np.sum(x, axis, where=mask) adds the pairwise sum of every maximal run
-// of selected elements to ONE float32 accumulator, run after run (reduce_exact.hip's header) -- a
+// of selected elements to ONE float32 accumulator, run after run (numpy_sum.h's header) -- a
 // chain of len * p * (1 - p) dependent additions per row and mask (1024 for a 4096-element row when
 // the guess is 0). octav_rows_kernel gave every row a workgroup and walked its two chains on two
 // lanes of one wave: a wave issues one dependent addition per ~5 cycles whatever its lanes do, so
