@@ -8,6 +8,11 @@
 // store consecutive units (a wave stores 1 KB in one piece on the vector route); the loads are contiguous within a
 // tap and the input is re-read KH KW / (stride_h stride_w) times, from L2. The unit index is 32-bit where the launch
 // fits (the divisions are the kernel's only arithmetic), 64-bit with a grid stride otherwise; every address is 64-bit.
+//
+// The gather in front of TRANSPOSE_CONV ("Patch gather for TRANSPOSE_CONV") is the same kernel: one sub-pixel phase of
+// a transposed convolution is a stride-1 gather whose taps walk the image backwards (a = qy + base - ti), which is
+// move_unit with stride 1, a dilation of -1 and pad_top = -base. The host entry works the phase's tap counts and bases
+// out; the kernel divides by no stride. mi355q_conv_patches_nhwc itself still refuses a dilation below 1.
 #include "common.h"
 
 namespace mi355q {
@@ -68,6 +73,34 @@ void launch(const PatchArgs& g, T pad, hipStream_t st) {
   }
 }
 
+// What both entries do once their arguments are checked: pick the route by C and the two addresses, count the units and
+// launch. `g` holds the geometry (H, W, KW, OW, OHW, first_row, strides, dilations, paddings); K = taps C.
+void enqueue(PatchArgs g, const void* x, void* out, int32_t elem_bytes, int64_t C, int64_t K, int64_t row_count,
+             const void* pad_element, hipStream_t st) {
+  const bool vec = (C * elem_bytes) % 16 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
+  const int unit = vec ? 16 : elem_bytes;
+  g.x = x; g.out = out;
+  g.row_units = static_cast<uint32_t>(K * elem_bytes / unit);
+  g.tap_units = static_cast<uint32_t>(C * elem_bytes / unit);
+  g.total = static_cast<uint64_t>(row_count) * g.row_units;
+  if (vec) {
+    uint4 pad;
+    unsigned char* b = reinterpret_cast<unsigned char*>(&pad);
+    for (int i = 0; i < 16; ++i) b[i] = static_cast<const unsigned char*>(pad_element)[i % elem_bytes];
+    launch<uint4>(g, pad, st);
+  } else if (elem_bytes == 1) {
+    launch<uint8_t>(g, *static_cast<const uint8_t*>(pad_element), st);
+  } else if (elem_bytes == 2) {
+    uint16_t pad;
+    __builtin_memcpy(&pad, pad_element, 2);
+    launch<uint16_t>(g, pad, st);
+  } else {
+    uint32_t pad;
+    __builtin_memcpy(&pad, pad_element, 4);
+    launch<uint32_t>(g, pad, st);
+  }
+}
+
 }  // namespace
 }  // namespace mi355q
 
@@ -105,33 +138,93 @@ extern "C" int32_t mi355q_conv_patches_nhwc(const void* x, int32_t elem_bytes, i
   if (row_count == 0) return MI355Q_OK;
   if (!x || !out || !pad_element) return fail(MI355Q_BAD_ARG, "null pointer");
 
-  const bool vec = (C * elem_bytes) % 16 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-  const int unit = vec ? 16 : elem_bytes;
   PatchArgs g{};
-  g.x = x; g.out = out; g.H = H; g.W = W;
-  g.row_units = static_cast<uint32_t>(K * elem_bytes / unit);
-  g.tap_units = static_cast<uint32_t>(C * elem_bytes / unit);
-  g.total = static_cast<uint64_t>(row_count) * g.row_units;
+  g.H = H; g.W = W;
   g.KW = static_cast<uint32_t>(KW); g.OW = static_cast<uint32_t>(OW); g.OHW = static_cast<uint32_t>(OH * OW);
   g.first_row = static_cast<uint32_t>(first_row);
   g.stride_h = stride_h; g.stride_w = stride_w; g.dil_h = dil_h; g.dil_w = dil_w; g.pad_top = pad_top; g.pad_left = pad_left;
-  hipStream_t st = as_stream(stream);
-  if (vec) {
-    uint4 pad;
-    unsigned char* b = reinterpret_cast<unsigned char*>(&pad);
-    for (int i = 0; i < 16; ++i) b[i] = static_cast<const unsigned char*>(pad_element)[i % elem_bytes];
-    launch<uint4>(g, pad, st);
-  } else if (elem_bytes == 1) {
-    launch<uint8_t>(g, *static_cast<const uint8_t*>(pad_element), st);
-  } else if (elem_bytes == 2) {
-    uint16_t pad;
-    __builtin_memcpy(&pad, pad_element, 2);
-    launch<uint16_t>(g, pad, st);
-  } else {
-    uint32_t pad;
-    __builtin_memcpy(&pad, pad_element, 4);
-    launch<uint32_t>(g, pad, st);
-  }
+  enqueue(g, x, out, elem_bytes, C, K, row_count, pad_element, as_stream(stream));
   MI355Q_CHECK_LAUNCH("conv patch gather launch");
+  return MI355Q_OK;
+}
+
+namespace {
+
+// One axis of a TRANSPOSE_CONV geometry: the forward convolution (kernel K, stride s, no dilation) from the OUTPUT
+// size `out` back to the input size `in`, by TFLite's rule, with pad_before = `pad`. SAME: in = ceil(out / s);
+// VALID: in = (out + s - K) / s; pad_before = max(0, (in - 1) s + K - out) / 2 under both.
+bool forward_axis_ok(int64_t in, int64_t out, int64_t K, int64_t s, int64_t pad) {
+  const bool same = in == (out + s - 1) / s;
+  const bool valid = out + s - K >= s && in == (out + s - K) / s;
+  const int64_t total = (in - 1) * s + K - out;      // (in, out <= INT32_MAX and K, s are int32: no overflow)
+  return (same || valid) && pad == (total > 0 ? total : 0) / 2;
+}
+
+// The taps of one phase along one axis: ky = r, r + s, ... < K with r = (phase + pad) % s, in ascending order. Tap ti
+// reads input a = q + base - ti with base = (phase + pad) / s, so the kernel divides by no stride.
+struct PhaseAxis {
+  int64_t taps, base, rows;      // rows: the q with q s + phase < out
+};
+
+PhaseAxis phase_axis(int64_t out, int64_t K, int64_t s, int64_t pad, int64_t phase) {
+  const int64_t r = (phase + pad) % s;
+  PhaseAxis a;
+  a.taps = r < K ? (K - r + s - 1) / s : 0;
+  a.base = (phase + pad) / s;
+  a.rows = phase < out ? (out - phase + s - 1) / s : 0;
+  return a;
+}
+
+}  // namespace
+
+extern "C" int32_t mi355q_tconv_patches_nhwc(const void* x, int32_t elem_bytes, int64_t N, int64_t IH, int64_t IW, int64_t C,
+                                             int32_t KH, int32_t KW, int32_t stride_h, int32_t stride_w, int32_t pad_top,
+                                             int32_t pad_left, int64_t OH, int64_t OW, int32_t phase_h, int32_t phase_w,
+                                             int64_t first_row, int64_t row_count, const void* pad_element, void* out,
+                                             void* stream) {
+  clear_error();
+  if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4)
+    return fail(MI355Q_BAD_ARG, "elem_bytes must be 1, 2 or 4 (got %d)", elem_bytes);
+  if (N <= 0 || IH <= 0 || IW <= 0 || C <= 0 || KH <= 0 || KW <= 0 || OH <= 0 || OW <= 0)
+    return fail(MI355Q_BAD_ARG, "every dimension must be positive (N %lld, IH %lld, IW %lld, C %lld, KH %d, KW %d, OH %lld, OW %lld)",
+                static_cast<long long>(N), static_cast<long long>(IH), static_cast<long long>(IW), static_cast<long long>(C),
+                KH, KW, static_cast<long long>(OH), static_cast<long long>(OW));
+  if (stride_h <= 0 || stride_w <= 0) return fail(MI355Q_BAD_ARG, "strides must be positive (got %d, %d)", stride_h, stride_w);
+  if (phase_h < 0 || phase_h >= stride_h || phase_w < 0 || phase_w >= stride_w)
+    return fail(MI355Q_BAD_ARG, "phase (%d, %d) is outside the strides (%d, %d)", phase_h, phase_w, stride_h, stride_w);
+  if (first_row < 0 || row_count < 0) return fail(MI355Q_BAD_ARG, "negative row window");
+  if (OH > INT32_MAX || OW > INT32_MAX || N > INT32_MAX || IH > INT32_MAX || IW > INT32_MAX)
+    return fail(MI355Q_UNSUPPORTED, "N, IH, IW, OH or OW exceeds INT32_MAX");
+  if (pad_top < 0 || pad_left < 0 || !forward_axis_ok(IH, OH, KH, stride_h, pad_top) || !forward_axis_ok(IW, OW, KW, stride_w, pad_left))
+    return fail(MI355Q_BAD_ARG, "the forward convolution (kernel %d x %d, strides %d, %d, paddings %d, %d) does not map the output"
+                " %lld x %lld to the input %lld x %lld", KH, KW, stride_h, stride_w, pad_top, pad_left,
+                static_cast<long long>(OH), static_cast<long long>(OW), static_cast<long long>(IH), static_cast<long long>(IW));
+  const PhaseAxis ph = phase_axis(OH, KH, stride_h, pad_top, phase_h), pw = phase_axis(OW, KW, stride_w, pad_left, phase_w);
+  if (ph.taps == 0 || pw.taps == 0)
+    return fail(MI355Q_UNSUPPORTED, "phase (%d, %d) has no tap (a stride exceeds the kernel)", phase_h, phase_w);
+  const int64_t taps = ph.taps * pw.taps;      // (each <= INT32_MAX)
+  if (taps > kMaxK || C > kMaxK || taps * C > kMaxK)
+    return fail(MI355Q_UNSUPPORTED, "K = taps C of the phase exceeds %lld (the forward entries' limit)", static_cast<long long>(kMaxK));
+  const int64_t K = taps * C;
+  if (ph.rows * pw.rows > INT32_MAX || ph.rows * pw.rows * N > INT32_MAX)
+    return fail(MI355Q_UNSUPPORTED, "N QH QW exceeds INT32_MAX patch rows");
+  const int64_t rows_all = ph.rows * pw.rows * N;
+  if (first_row > rows_all || row_count > rows_all - first_row)
+    return fail(MI355Q_BAD_ARG, "rows [%lld, %lld + %lld) are outside the %lld patch rows of the phase", static_cast<long long>(first_row),
+                static_cast<long long>(first_row), static_cast<long long>(row_count), static_cast<long long>(rows_all));
+  // (N IH IW <= 2 N QH QW + N: with C <= 65536 the activation stays far below the CONV_2D entry's 2^62 bytes)
+  if (row_count == 0) return MI355Q_OK;
+  if (!x || !out || !pad_element) return fail(MI355Q_BAD_ARG, "null pointer");
+
+  // The phase as a stride-1 gather that walks the image backwards: a = qy + base_h - ti is move_unit's
+  // oh stride_h - pad_top + kh dil_h with stride 1, pad_top = -base_h and dil_h = -1.
+  PatchArgs g{};
+  g.H = IH; g.W = IW;
+  g.KW = static_cast<uint32_t>(pw.taps); g.OW = static_cast<uint32_t>(pw.rows); g.OHW = static_cast<uint32_t>(ph.rows * pw.rows);
+  g.first_row = static_cast<uint32_t>(first_row);
+  g.stride_h = 1; g.stride_w = 1; g.dil_h = -1; g.dil_w = -1;
+  g.pad_top = -static_cast<int32_t>(ph.base); g.pad_left = -static_cast<int32_t>(pw.base);
+  enqueue(g, x, out, elem_bytes, C, K, row_count, pad_element, as_stream(stream));
+  MI355Q_CHECK_LAUNCH("transposed conv patch gather launch");
   return MI355Q_OK;
 }

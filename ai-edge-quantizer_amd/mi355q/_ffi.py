@@ -146,6 +146,8 @@ PROTOTYPES = {
                                       c_ptr, c_ptr, c_size, c_ptr]),
     "mi355q_conv_patches_nhwc": (c_i32, [c_ptr, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                          c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
+    "mi355q_tconv_patches_nhwc": (c_i32, [c_ptr, c_i32, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
+                                          c_i64, c_i64, c_i32, c_i32, c_i64, c_i64, c_ptr, c_ptr, c_ptr]),
     "mi355q_dwconv_forward_f32": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32,
                                           c_i32, c_i32, c_i32, c_i64, c_i64, c_i64, c_i64, c_ptr, c_ptr]),
     "mi355q_dwconv_forward_i8": (c_i32, [c_ptr, c_i64, c_i64, c_i64, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i32, c_i32,

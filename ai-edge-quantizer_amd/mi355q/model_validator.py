@@ -480,16 +480,17 @@ def _as_model(model) -> Any:
   return model if hasattr(model, "subgraphs") else _model(model)
 
 
-def _ops_of_kind(m, sg_index: int, builtin: int, present: tuple = ()):
-  """(op, input 0 name, input 1 tensor, output name) of every op of kind `builtin` of a subgraph that has two inputs,
-  those numbered in `present` not absent (-1)."""
+def _ops_of_kind(m, sg_index: int, builtin: int, present: tuple = (), activation: int = 0, constant: int = 1):
+  """(op, input `activation` name, input `constant` tensor, output name) of every op of kind `builtin` of a subgraph that
+  has those inputs, the ones numbered in `present` not absent (-1). The defaults are the positions of FULLY_CONNECTED,
+  the two convolutions and BATCH_MATMUL; TRANSPOSE_CONV passes activation 2."""
   sg = m.subgraphs[sg_index]
   out = []
   for op in sg.operators or []:
-    if (int(m.operatorCodes[op.opcodeIndex].builtinCode) != builtin or len(op.inputs) < 2
+    if (int(m.operatorCodes[op.opcodeIndex].builtinCode) != builtin or len(op.inputs) <= max(activation, constant, 1)
         or any(op.inputs[i] < 0 for i in present)):
       continue
-    out.append((op, schema.tensor_name(sg.tensors[op.inputs[0]]), sg.tensors[op.inputs[1]],
+    out.append((op, schema.tensor_name(sg.tensors[op.inputs[activation]]), sg.tensors[op.inputs[constant]],
                 schema.tensor_name(sg.tensors[op.outputs[0]])))
   return out
 
@@ -952,6 +953,43 @@ def _depthwise_conv_2d_ops(m, sg_index: int):
   return _ops_of_kind(m, sg_index, _DEPTHWISE_CONV_2D, present=(0, 1))
 
 
+# `transpose_conv`: TRANSPOSE_CONV ops, executed by sub-pixel phases on patch rows (csrc/conv_patches.hip). The op reads
+# (output_shape, filter [O, KH, KW, I], activation, bias): the activation is input 2 and the bias input 3.
+_TRANSPOSE_CONV = 67
+_TRANSPOSE_CONV_OPTIONS_TYPE = 49      # TransposeConvOptions in the BuiltinOptions union
+_TCONV_OUTPUT_SHAPE, _TCONV_FILTER, _TCONV_ACTIVATION, _TCONV_BIAS = 0, 1, 2, 3
+SKIP_TCONV_OUTPUT_SHAPE = ("output_shape is not a constant INT32 [4] (the same in both models), or its batch / channels"
+                           " disagree with the sample / filter")
+SKIP_TCONV_UNREACHABLE = "output_shape is not reachable from the sample's H x W under the op's padding and strides"
+SKIP_TCONV_STRIDE = "a stride exceeds the kernel: some output pixels have no tap"
+SKIP_TCONV_MISMATCH = "the float op and the target op disagree about padding or strides"
+SKIP_TCONV_FILTER_SCALES = "the target filter is not int8 with scales per tensor or per channel along dimension 0"
+_TRANSPOSE_CONV_OPTION_FIELDS = (("padding", "padding", "i8", 0), ("stride_w", "strideW", "i32", 0),
+                                 ("stride_h", "strideH", "i32", 0),
+                                 ("fused_activation_function", "fusedActivationFunction", "i8", 0))
+
+
+def transpose_conv_options(op) -> Optional[dict]:
+  """TransposeConvOptions of a TRANSPOSE_CONV op as {padding (0 SAME, 1 VALID), stride_w, stride_h,
+  fused_activation_function}, in the schema's field order (ids 0 to 3; the op has no dilation), read as
+  conv_2d_options reads Conv2DOptions: from an OpaqueTableT by field id with the schema's defaults (0) for absent
+  fields when the op's builtinOptionsType is 49, or from a decoded object with the generated API's attribute names
+  (one that also has dilationWFactor is a convolution's); an op without options has every default. None when the op
+  carries the options of another op type."""
+  if op.builtinOptions is not None and hasattr(op.builtinOptions, "dilationWFactor"):
+    return None
+  return _table_options(op, _TRANSPOSE_CONV_OPTION_FIELDS, _TRANSPOSE_CONV_OPTIONS_TYPE, "strideW")
+
+
+_transpose_conv_option = _fused_option(transpose_conv_options)      # (_conv_option for a TRANSPOSE_CONV)
+
+
+def _transpose_conv_ops(m, sg_index: int):
+  """(op, input 2 name, filter tensor, output name) of every TRANSPOSE_CONV op of a subgraph."""
+  return _ops_of_kind(m, sg_index, _TRANSPOSE_CONV, present=(_TCONV_OUTPUT_SHAPE, _TCONV_FILTER, _TCONV_ACTIVATION),
+                      activation=_TCONV_ACTIVATION)
+
+
 # `batch_matmul`: BATCH_MATMUL ops, executed by the integer batched product (csrc/qbmm.hip)
 _BATCH_MATMUL = 126
 SKIP_BMM_RANK = "an operand has rank below 2, or the two operands disagree about K"
@@ -1039,9 +1077,10 @@ def _multiplier_table(s_x: float, w_scale: np.ndarray, s_y: float, bits: int):
 
 
 def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x: float, w_scale: np.ndarray,
-                 option=_fc_option):
+                 option=_fc_option, bias_index: int = 2):
   """An OutputPlan, or the FINAL_SKIP_* reason there is none. `option(op, field)` reads an op's options
-  (_conv_option for a CONV_2D and _depthwise_option for a DEPTHWISE_CONV_2D, whose FC-only fields are default)."""
+  (_conv_option for a CONV_2D and _depthwise_option for a DEPTHWISE_CONV_2D, whose FC-only fields are default).
+  `bias_index`: the input that is the bias, 2 for every kind but TRANSPOSE_CONV (3)."""
   from . import ops
   if option(fc, "weightsFormat") != 0 or option(ref_op, "weightsFormat") != 0:
     return FINAL_SKIP_WEIGHTS_FORMAT
@@ -1054,10 +1093,10 @@ def _output_plan(ref, ref_sg, ref_op, tgt, tgt_sg, fc, rows: int, bits: int, s_x
   s_y, zp_y = grid
   # ---- the two biases
   def constant(m, sg, op, ttype) -> Any:
-    """The op's input 2 as a flat array of `ttype`, None when absent, False when it is something else."""
-    if len(op.inputs) < 3 or op.inputs[2] < 0:
+    """The op's bias input as a flat array of `ttype`, None when absent, False when it is something else."""
+    if len(op.inputs) <= bias_index or op.inputs[bias_index] < 0:
       return None
-    t = sg.tensors[op.inputs[2]]
+    t = sg.tensors[op.inputs[bias_index]]
     if t.type != ttype or not _has_data(m.buffers, t) or _numel(t) != rows:
       return False
     return np.ascontiguousarray(_raw_bytes(m.buffers, t)).view(schema.NUMPY_DTYPE[ttype])[:rows].copy()
@@ -1141,6 +1180,20 @@ class LayerExecutionKernels:
     q, scale = ops.qfc_quantize_rows(x.view(n, -1))
     image = torch.arange(n * patch_rows, device=x.device) // patch_rows
     return q.view(x.shape), scale[image]
+
+  # (`transpose_conv`: one sub-pixel phase (py, px) at a time; its rows are (n, qy, qx), QH QW per image)
+  def tconv_patches(self, x, kernel: tuple, strides: tuple, padding: str, out_hw: tuple, phase: tuple, pad_value, first: int,
+                    count: int):
+    """Rows first .. first + count - 1 of the [N QH QW, |kys| |kxs| C] patch rows of `phase` of x [N, IH, IW, C], in
+    x's own type, taps outside the image holding `pad_value` (ops.tconv_patches)."""
+    from . import ops
+    return ops.tconv_patches(x, kernel[0], kernel[1], strides, padding, out_hw, phase, pad_value, first, count)
+
+  def image_scales(self, scale, rows_per_image: int, first: int, count: int):
+    """float32 [count]: the scale of the image each of the rows first .. first + count - 1 belongs to, `rows_per_image`
+    rows per image in order (`scale` has one entry per image). The index is formed on the device."""
+    import torch
+    return scale[torch.arange(first, first + count, device=scale.device) // rows_per_image]
 
   # (`depthwise_conv_2d`: x [N, H, W, C] float32 / int8 / int16; rows first .. first + count - 1 of the N OH OW output
   # rows as [count, O]; `kernel` (KH, KW); the filter is [KH KW, O], the stored bytes of TFLite's [1, KH, KW, O])
@@ -1305,6 +1358,8 @@ class LayerExecutionComparison(LayerOutputComparison):
   rows) `kernel`, `strides`, `dilations`, `padding` and `output_hw`;
   with `depthwise_conv_2d` also `op` (then also "DEPTHWISE_CONV_2D"), and for such an op the keys of a CONV_2D entry
   (rows = O, d = KH KW, tokens = output rows) and `depth_multiplier`;
+  with `transpose_conv` also `op` (then also "TRANSPOSE_CONV"), and for such an op the keys of a CONV_2D entry without
+  `dilations` (rows = O, d = KH KW I, tokens = output pixels) and `phases`;
   `skipped[name]` is the reason an op was not computed."""
 
   def as_dict(self) -> dict:
@@ -1331,7 +1386,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
                             quantized_outputs: bool = False,
                             conv_2d: bool = False,
                             depthwise_conv_2d: bool = False,
-                            batch_matmul: bool = False) -> LayerExecutionComparison:
+                            batch_matmul: bool = False,
+                            transpose_conv: bool = False) -> LayerExecutionComparison:
   """Executes every quantized FULLY_CONNECTED op in integers on the calibration samples and compares it with the
   float model's product, for every op of the float model with a constant 2-D float32 weight [rows, d] whose input 0
   is in `samples` (the {tensor name: array or device tensor} maps calibrate() takes; tensors of any rank are rows of
@@ -1440,13 +1496,44 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
   SKIP_INT16, a constant with a zero point SKIP_WEIGHT_ZERO_POINT. The arithmetic is this library's own definition,
   modelled on LiteRT's BATCH_MATMUL; agreement with LiteRT's kernels is unchecked. Every entry carries `op` whenever
   this or a conv keyword is on.
+
+  With `transpose_conv` every TRANSPOSE_CONV op of the float model is executed as well. The op reads (output_shape,
+  filter, x, bias): its activation is input 2 and its bias input 3; the filter is a constant float32 [O, KH, KW, I],
+  output_shape a constant INT32 [N, OH, OW, O] (the same in both models), and input 2 has samples of rank 4,
+  [N, IH, IW, I]. With (pad_top, pad_left) the padding of the FORWARD convolution from the OUTPUT image back to the
+  input (ops.tconv_geometry, from the op's TransposeConvOptions: transpose_conv_options; the op has no dilation),
+    out[n, oy, ox, o] = Sum_{ky, kx, i} x[n, a, b, i] W[o, ky, kx, i]
+  over the taps with (oy + pad_top - ky) % sh == 0 and a = (oy + pad_top - ky) / sh in [0, IH), likewise b. It is
+  executed by SUB-PIXEL PHASES (ops.tconv_phases): the output pixels oy = qy sh + py, ox = qx sw + px of one phase all
+  use the same taps kys x kxs, so the phase is the product above of its [N QH QW, |kys| |kxs| I] patch rows
+  (ops.tconv_patches) with the filter slice W[:, kys][:, :, kxs], a [rows = O, |kys| |kxs| I] weight whose per-channel
+  scales along dimension 0 are untouched by the slice; gathering full KH KW I rows over a zero-stuffed input instead
+  would multiply sh sw - 1 of every sh sw taps by nothing. The float filter and the stored integers are sliced per
+  phase on the host, once; the op then runs phase by phase, each in chunks of at most 4096 rows, and every chunk's
+  sums are added into the op's one set of float64 sums in that fixed order. Y = patches(X, pad 0.0) slice^T. The mode
+  is read as for CONV_2D. "static": the whole sample is quantized once with the tensor's (s_x, zp_x), 8 or 16 bits,
+  and every phase gathers from the INTEGER tensor with pad element zp_x. "dynamic": one scale per batch element,
+  every image quantized as a whole, and every row of every phase takes its image's scale. "weight_only":
+  patches(X) dequant(slice)^T. With `quantized_outputs` the unchanged epilogue runs on each phase's rows (the bias is
+  input 3, the fused activation read from TransposeConvOptions) and the final sums are added the same way; no
+  interleaved output tensor is formed. The filter is int8, per tensor or per channel along dimension 0. This is the
+  library's own definition, modelled on LiteRT's TRANSPOSE_CONV and unchecked against it. An entry carries the keys of
+  a conv entry with `op` = "TRANSPOSE_CONV", `rows` = O, `d` = KH KW I, `tokens` = Sum N OH OW, `output_hw`, no
+  `dilations`, and `phases` (the number executed); EVERY entry carries `op` whenever this keyword is on. Further skip
+  reasons: SKIP_TCONV_OUTPUT_SHAPE (output_shape is no constant INT32 [4], or its batch / channels disagree with the
+  sample / filter), SKIP_TCONV_UNREACHABLE (output_shape is not reachable from the sample's H x W under the op's
+  padding and strides), SKIP_TCONV_STRIDE (a stride exceeds the kernel, so some output pixels have no tap),
+  SKIP_TCONV_MISMATCH (the options differ between the two models), SKIP_TCONV_FILTER_SCALES (the filter is not int8,
+  is blockwise, or has scales off dimension 0); the reasons of CONV_2D that apply keep their texts. Without the
+  keyword nothing changes.
 """
   ref, tgt = _as_model(reference_model), _as_model(target_model)
   sg_ref, _ = _signature_subgraph(ref, signature_key)
   sg_tgt, _ = _signature_subgraph(tgt, signature_key)
   graph = _TargetGraph.of(tgt, tgt.subgraphs[sg_tgt])
   run = _ExecutionRun(ref, sg_ref, list(samples), kernels or LayerExecutionKernels(), follow_input_transforms,
-                      int16_activations, quantized_outputs, op_key=conv_2d or depthwise_conv_2d or batch_matmul)
+                      int16_activations, quantized_outputs,
+                      op_key=conv_2d or depthwise_conv_2d or batch_matmul or transpose_conv)
   out = LayerExecutionComparison(signature_key)
   _fully_connected_entries(out, graph, run)
   if conv_2d:
@@ -1455,6 +1542,8 @@ def compare_layer_execution(reference_model, target_model, samples: Iterable[dic
     _depthwise_conv_2d_entries(out, graph, run)
   if batch_matmul:
     _batch_matmul_entries(out, graph, run)
+  if transpose_conv:
+    _transpose_conv_entries(out, graph, run)
   return out
 
 
@@ -1506,10 +1595,11 @@ def _record(out: LayerExecutionComparison, y_name: str, entry) -> None:
     out.results[y_name] = entry
 
 
-def _target_op(graph: _TargetGraph, y_name: str, builtin: int):
-  """The target op of kind `builtin` that writes `y_name` and has inputs 0 and 1, or None."""
+def _target_op(graph: _TargetGraph, y_name: str, builtin: int, needed: tuple = (0, 1)):
+  """The target op of kind `builtin` that writes `y_name` and has the inputs `needed` (0 and 1; TRANSPOSE_CONV passes
+  0, 1 and 2), or None."""
   op = graph.producer_op.get(y_name)
-  if op is None or graph.code(op) != builtin or len(op.inputs) < 2 or op.inputs[0] < 0 or op.inputs[1] < 0:
+  if op is None or graph.code(op) != builtin or len(op.inputs) <= max(needed) or any(op.inputs[i] < 0 for i in needed):
     return None
   return op
 
@@ -1559,8 +1649,10 @@ def _quantized_activation(graph: _TargetGraph, index: int, want_name: str, *, in
 
 
 def _execution_mode(graph: _TargetGraph, op, x_name: str, through_dequantize: bool, *, int16: bool,
-                    zero_point_range: bool = True, transforms_d: Optional[int] = None, dequantize_first: bool = False):
-  """(mode, (scale, zero point, bits) or None, input transform) of a target op whose input 0 stands for the float
+                    zero_point_range: bool = True, transforms_d: Optional[int] = None, dequantize_first: bool = False,
+                    activation: int = 0):
+  """(mode, (scale, zero point, bits) or None, input transform) of a target op whose input `activation` (0 for every
+  kind but TRANSPOSE_CONV, which passes 2) stands for the float
   model's `x_name` and whose constant is read `through_dequantize` or not: a FLOAT32 input is "weight_only" behind a
   DEQUANTIZE and "dynamic" otherwise, a quantized one (_quantized_activation, which takes `int16` and
   `zero_point_range`) is "static" and goes with the integer constant itself.
@@ -1569,7 +1661,7 @@ def _execution_mode(graph: _TargetGraph, op, x_name: str, through_dequantize: bo
   and BATCH_MATMUL never follow.
   `dequantize_first`: BATCH_MATMUL passes True, a quantized input in front of a DEQUANTIZE'd constant is SKIP_INPUT
   before its type is looked at; for the other kinds an INT16 input without `int16_activations` is SKIP_INT16 first."""
-  index = op.inputs[0]
+  index = op.inputs[activation]
   if graph.tgt_sg.tensors[index].type == schema.TensorType.FLOAT32:
     mode = MODE_WEIGHT_ONLY if through_dequantize else MODE_DYNAMIC
     if graph.name(index) == x_name:
@@ -1615,19 +1707,21 @@ def _constant_plan(graph: _TargetGraph, ref, w, target, kinds: tuple, kind_reaso
 _CONV_GEOMETRY_OPTIONS = ("padding", "stride_h", "stride_w", "dilation_h_factor", "dilation_w_factor")
 
 
-def _conv_options(reader, conv, ref_op, also: tuple = (), mismatch_reason: str = SKIP_CONV_OPTIONS):
+def _conv_options(reader, conv, ref_op, also: tuple = (), mismatch_reason: str = SKIP_CONV_OPTIONS,
+                  geometry: tuple = _CONV_GEOMETRY_OPTIONS):
   """(options, strides, dilations, padding name) of a convolution whose float and target op agree about the geometry
-  and the fields `also` (else `mismatch_reason`: the depthwise op has one of its own), by `reader`."""
+  and the fields `also` (else `mismatch_reason`: the depthwise op has one of its own), by `reader`. `geometry`: the
+  option fields that make the geometry, padding first; TRANSPOSE_CONV has no dilations (they read as 1)."""
   from . import ops
   options, float_options = reader(conv), reader(ref_op)
   if options is None or float_options is None:
     return SKIP_CONV_OPTIONS
-  if any(options[k] != float_options[k] for k in _CONV_GEOMETRY_OPTIONS + also):
+  if any(options[k] != float_options[k] for k in geometry + also):
     return mismatch_reason
-  if options["padding"] not in ops.CONV_PADDING_NAMES or min(options[k] for k in _CONV_GEOMETRY_OPTIONS[1:]) < 1:
+  if options["padding"] not in ops.CONV_PADDING_NAMES or min(options[k] for k in geometry[1:]) < 1:
     return SKIP_CONV_OPTIONS
-  return (options, (options["stride_h"], options["stride_w"]), (options["dilation_h_factor"], options["dilation_w_factor"]),
-          ops.CONV_PADDING_NAMES[options["padding"]])
+  return (options, (options["stride_h"], options["stride_w"]),
+          (options.get("dilation_h_factor", 1), options.get("dilation_w_factor", 1)), ops.CONV_PADDING_NAMES[options["padding"]])
 
 
 def _output_shapes(present: list, kernel: tuple, strides: tuple, dilations: tuple, padding: str, d: int, max_d: int):
@@ -1653,14 +1747,21 @@ def _device_operands(graph: _TargetGraph, run: _ExecutionRun, ref_op, op, values
   w_dev = kernels.weight(values, *shape)
   t_dev = kernels.target(plan)
   dq_dev = kernels.dequantized(t_dev, *shape) if mode == MODE_WEIGHT_ONLY else None
+  return (w_dev, t_dev, dq_dev) + _final_operands(graph, run, ref_op, op, plan, rows, mode, quant, option)
+
+
+def _final_operands(graph: _TargetGraph, run: _ExecutionRun, ref_op, op, plan, rows: int, mode: str, quant, option,
+                    bias_index: int = 2):
+  """(OutputPlan / FINAL_SKIP_* / None, bias, float bias), the two biases on the device (_output_plan)."""
+  kernels = run.kernels
   final, bias_dev, float_bias_dev = None, None, None
   if run.quantized_outputs and mode == MODE_STATIC:
     final = _output_plan(run.ref, run.ref.subgraphs[run.sg_ref], ref_op, graph.tgt, graph.tgt_sg, op, rows, quant[2],
-                         quant[0], plan.scale, option=option)
+                         quant[0], plan.scale, option=option, bias_index=bias_index)
   if isinstance(final, OutputPlan):
     bias_dev = None if final.bias is None else kernels.bias(final.bias)
     float_bias_dev = None if final.float_bias is None else kernels.bias(final.float_bias)
-  return w_dev, t_dev, dq_dev, final, bias_dev, float_bias_dev
+  return final, bias_dev, float_bias_dev
 
 
 def _quantize_static(kernels, x, quant: tuple):
@@ -1721,7 +1822,7 @@ def _finish_entry(entry: dict, run: _ExecutionRun, mode: str, activation_bits: O
   return entry
 
 
-# ---- the four op kinds: each *_entry returns the op's entry, or the reason it has none
+# ---- the five op kinds: each *_entry returns the op's entry, or the reason it has none
 def _fully_connected_entries(out, graph: _TargetGraph, run: _ExecutionRun) -> None:
   for ref_op, x_name, w, y_name in _fully_connected_ops(run.ref, run.sg_ref):
     _record(out, y_name, _fully_connected_entry(graph, run, ref_op, x_name, w, y_name))
@@ -1862,6 +1963,127 @@ def _conv_2d_entry(graph: _TargetGraph, run: _ExecutionRun, ref_op, x_name: str,
   entry = {"op": "CONV_2D", "weight": schema.tensor_name(w), "input": x_name, "rows": rows, "d": d, "tokens": tokens,
            "mode": mode, "kernel": [kh, kw], "strides": list(strides), "dilations": list(dilations), "padding": padding,
            "output_hw": [shapes[0][0], shapes[0][1]], **_error_figures(kernels, sums, tokens, rows)}
+  return _finish_entry(entry, run, mode, quant and quant[2], transform, final, final_sums, tokens, rows)
+
+
+def _transpose_conv_entries(out, graph: _TargetGraph, run: _ExecutionRun) -> None:
+  """TRANSPOSE_CONV: the same product, one sub-pixel phase at a time (compare_layer_execution's section on
+  `transpose_conv`)."""
+  for ref_op, x_name, w, y_name in _transpose_conv_ops(run.ref, run.sg_ref):
+    _record(out, y_name, _transpose_conv_entry(graph, run, ref_op, x_name, w, y_name))
+
+
+def _constant_output_shape(m, sg, op):
+  """The four INT32 values of a TRANSPOSE_CONV op's constant output_shape (input 0), or None."""
+  t = sg.tensors[op.inputs[_TCONV_OUTPUT_SHAPE]]
+  if t.type != schema.TensorType.INT32 or not _has_data(m.buffers, t) or t.shape is None or list(t.shape) != [4]:
+    return None
+  return [int(v) for v in np.ascontiguousarray(_raw_bytes(m.buffers, t)).view(np.int32)[:4]]
+
+
+def _transpose_conv_entry(graph: _TargetGraph, run: _ExecutionRun, ref_op, x_name: str, w, y_name: str):
+  from . import ops
+  kernels, ref = run.kernels, run.ref
+  if (w.type != schema.TensorType.FLOAT32 or not _has_data(ref.buffers, w) or w.shape is None or len(w.shape) != 4
+      or min(int(v) for v in w.shape) < 1):
+    return SKIP_CONV_FILTER
+  rows, kh, kw, channels = (int(v) for v in w.shape)
+  d = kh * kw * channels
+  tconv = _target_op(graph, y_name, _TRANSPOSE_CONV, needed=(_TCONV_OUTPUT_SHAPE, _TCONV_FILTER, _TCONV_ACTIVATION))
+  if tconv is None:
+    return SKIP_TARGET
+  found = _conv_options(transpose_conv_options, tconv, ref_op, mismatch_reason=SKIP_TCONV_MISMATCH,
+                        geometry=("padding", "stride_h", "stride_w"))
+  if isinstance(found, str):
+    return found
+  _, strides, _, padding = found
+  out_shape = _constant_output_shape(ref, ref.subgraphs[run.sg_ref], ref_op)
+  if out_shape is None or out_shape != _constant_output_shape(graph.tgt, graph.tgt_sg, tconv) or out_shape[3] != rows:
+    return SKIP_TCONV_OUTPUT_SHAPE
+  out_hw = (out_shape[1], out_shape[2])
+  found = _target_constant(graph, tconv, schema.tensor_name(w), rows * d)
+  if isinstance(found, str):
+    return found
+  target, through_dequantize = found
+  found = _execution_mode(graph, tconv, x_name, through_dequantize, int16=run.int16_activations,
+                          activation=_TCONV_ACTIVATION)
+  if isinstance(found, str):
+    return found
+  mode, quant, transform = found
+  # the filter as a [O, K] constant, K = KH KW I contiguous per output channel: per-channel scales along dimension 0
+  # stay what they are under a slice of the taps
+  found = _constant_plan(graph, ref, w, target, ("i8",), SKIP_TCONV_FILTER_SCALES, SKIP_TCONV_FILTER_SCALES, axis=(rows, d),
+                         axis_reason=SKIP_TCONV_FILTER_SCALES, scale_count=True)
+  if isinstance(found, str):
+    return found
+  values, plan = found
+  present = [s[x_name] for s in run.samples if x_name in s]
+  if not present:
+    return SKIP_NO_SAMPLE
+  if any(len(v.shape) != 4 for v in present):
+    return SKIP_SAMPLE_SHAPE
+  if any(int(v.shape[3]) != channels for v in present):
+    return SKIP_CONV_GROUPS
+  present = [v for v in present if int(v.shape[0]) > 0]
+  if not present:
+    return SKIP_NO_SAMPLE
+  if any(int(v.shape[0]) != out_shape[0] for v in present):
+    return SKIP_TCONV_OUTPUT_SHAPE
+  if d > ops.QFC_MAX_D or min(out_hw) < 1:
+    return SKIP_CONV_GEOMETRY
+  try:
+    for v in present:
+      ops.tconv_geometry(int(v.shape[1]), int(v.shape[2]), kh, kw, strides, padding, out_hw)
+  except ValueError:
+    return SKIP_TCONV_UNREACHABLE
+  # (the forward convolution maps out_hw to ONE input size, so every sample has the first one's phases)
+  phases = ops.tconv_phases(int(present[0].shape[1]), int(present[0].shape[2]), kh, kw, strides, padding, out_hw)
+  if any(not kys or not kxs for *_, kys, kxs in phases):
+    return SKIP_TCONV_STRIDE
+  # the float filter and the stored integers, sliced per phase on the host, once
+  w4, q4 = values.reshape(rows, kh, kw, channels), np.asarray(plan.data).reshape(rows, kh, kw, channels)
+  w_dev, t_dev, dq_dev = [], [], []
+  for *_, kys, kxs in phases:
+    k_p = len(kys) * len(kxs) * channels
+    w_p = np.ascontiguousarray(w4[:, list(kys)][:, :, list(kxs)]).reshape(-1)
+    q_p = np.ascontiguousarray(q4[:, list(kys)][:, :, list(kxs)]).reshape(-1)
+    w_dev.append(kernels.weight(w_p, rows, k_p))
+    t_dev.append(kernels.target(dataclasses.replace(plan, reference=w_p, data=q_p, inner=k_p if plan.channels == rows else 1)))
+    dq_dev.append(kernels.dequantized(t_dev[-1], rows, k_p) if mode == MODE_WEIGHT_ONLY else None)
+  final, bias_dev, float_bias_dev = _final_operands(graph, run, ref_op, tconv, plan, rows, mode, quant, _transpose_conv_option,
+                                                    bias_index=_TCONV_BIAS)
+  sums, final_sums, tokens = None, None, 0
+  pad = quant[1] if mode == MODE_STATIC and quant[2] == 8 else 0
+  for value in present:
+    x = kernels.sample4d(value)
+    n_img = int(x.shape[0])
+    # as for CONV_2D the whole sample is quantized ONCE and every phase gathers from the integer tensor, padded with the
+    # zero point; a dynamic op has one scale per image, which every row of every phase of that image takes
+    if mode == MODE_DYNAMIC:
+      xq_all, image_scale = kernels.quantize_dynamic_images(x, 1)
+    elif mode == MODE_STATIC:
+      xq_all, x_scale = _quantize_static(kernels, x, quant)
+    for p, (py, px, qh, qw, kys, kxs) in enumerate(phases):
+      n, k_p = n_img * qh * qw, len(kys) * len(kxs) * channels
+      gather = (kh, kw), strides, padding, out_hw, (py, px)
+      for first in range(0, n, EXECUTION_CHUNK_ROWS):
+        count = min(EXECUTION_CHUNK_ROWS, n - first)
+        xc = kernels.tconv_patches(x, *gather, 0.0, first, count)
+        y = kernels.gemm(xc, w_dev[p])
+        if mode == MODE_WEIGHT_ONLY:
+          yq = kernels.gemm(xc, dq_dev[p])
+        else:
+          xq = kernels.tconv_patches(xq_all, *gather, pad, first, count)
+          scale = kernels.image_scales(image_scale, qh * qw, first, count) if mode == MODE_DYNAMIC else x_scale
+          yq = _forward(kernels, xq, scale, quant, t_dev[p], rows, k_p)
+        sums = kernels.sqdiff(yq, y, sums)
+        if isinstance(final, OutputPlan):
+          q_out = _stored_output(kernels, final, xq, quant[1], t_dev[p], rows, k_p, bias_dev)
+          final_sums = _final_sqdiff(kernels, final, q_out, y, float_bias_dev, final_sums)
+    tokens += n_img * out_hw[0] * out_hw[1]
+  entry = {"op": "TRANSPOSE_CONV", "weight": schema.tensor_name(w), "input": x_name, "rows": rows, "d": d, "tokens": tokens,
+           "mode": mode, "kernel": [kh, kw], "strides": list(strides), "padding": padding, "output_hw": list(out_hw),
+           "phases": len(phases), **_error_figures(kernels, sums, tokens, rows)}
   return _finish_entry(entry, run, mode, quant and quant[2], transform, final, final_sums, tokens, rows)
 
 

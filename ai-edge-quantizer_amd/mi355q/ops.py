@@ -1328,6 +1328,19 @@ def conv_geometry(h: int, w: int, kh: int, kw: int, stride, dilation, padding) -
   return oh, ow, top, left
 
 
+def _pad_element(pad_value, np_dtype):
+  """One pad element of `np_dtype` as the host bytes the patch gathers read."""
+  pad = np.asarray(pad_value)
+  if pad.size != 1:
+    raise ValueError("pad_value must be one element")
+  if pad.dtype != np_dtype:
+    if np_dtype != np.float32:
+      if pad.dtype.kind not in "iub" or not np.iinfo(np_dtype).min <= int(pad.reshape(())) <= np.iinfo(np_dtype).max:
+        raise ValueError(f"pad_value {pad_value!r} is no {np.dtype(np_dtype).name}")
+    pad = pad.astype(np_dtype)
+  return ctypes.create_string_buffer(pad.tobytes(), pad.itemsize)
+
+
 def conv_patches(x: torch.Tensor, kh: int, kw: int, stride, dilation, padding, pad_value=0, first: int = 0,
                  count: int | None = None) -> torch.Tensor:
   """The patch rows of an NHWC activation: x [N, H, W, C] (int8, int16 or float32, on the device) ->
@@ -1358,16 +1371,7 @@ def conv_patches(x: torch.Tensor, kh: int, kw: int, stride, dilation, padding, p
   count = rows_all - first if count is None else int(count)
   if first < 0 or count < 0 or first + count > rows_all:
     raise ValueError(f"rows [{first}, {first} + {count}) are outside the {rows_all} patch rows")
-  np_dtype = _CONV_DTYPES[x.dtype]
-  pad = np.asarray(pad_value)
-  if pad.size != 1:
-    raise ValueError("pad_value must be one element")
-  if pad.dtype != np_dtype:
-    if np_dtype != np.float32:
-      if pad.dtype.kind not in "iub" or not np.iinfo(np_dtype).min <= int(pad.reshape(())) <= np.iinfo(np_dtype).max:
-        raise ValueError(f"pad_value {pad_value!r} is no {np.dtype(np_dtype).name}")
-    pad = pad.astype(np_dtype)
-  pad_bytes = ctypes.create_string_buffer(pad.tobytes(), pad.itemsize)
+  pad_bytes = _pad_element(pad_value, _CONV_DTYPES[x.dtype])
   if not x.is_contiguous():
     x = x.contiguous()
   out = rt.empty((count, k), x.dtype)
@@ -1375,6 +1379,248 @@ def conv_patches(x: torch.Tensor, kh: int, kw: int, stride, dilation, padding, p
                                                  left, oh, ow, first, count, ctypes.cast(pad_bytes, ctypes.c_void_p),
                                                  rt.ptr(out), rt.stream_ptr()))
   return out
+
+
+# (include/mi355q.h, "Patch gather for TRANSPOSE_CONV")
+def tconv_geometry(ih: int, iw: int, kh: int, kw: int, stride, padding, out_hw) -> tuple:
+  """(pad_top, pad_left) of a TRANSPOSE_CONV from an ih x iw image to `out_hw` = (OH, OW): the padding of the FORWARD
+  convolution from the OUTPUT image back to the input (TFLite's rule, no dilation), host arithmetic:
+  conv_geometry(OH, OW, kh, kw, stride, 1, padding) must return exactly (ih, iw, pad_top, pad_left). Raises ValueError
+  when it does not: `out_hw` is not reachable from ih x iw under this padding and these strides."""
+  oh, ow = _pair(out_hw, "out_hw")
+  back = conv_geometry(oh, ow, kh, kw, stride, 1, padding)
+  if back[:2] != (int(ih), int(iw)):
+    raise ValueError(f"a {_padding_name(padding)} convolution ({int(kh)} x {int(kw)}, strides {_pair(stride, 'stride')}) maps the output"
+                     f" {oh} x {ow} to {back[0]} x {back[1]}, not to the input {int(ih)} x {int(iw)}")
+  return back[2], back[3]
+
+
+def tconv_phases(ih: int, iw: int, kh: int, kw: int, stride, padding, out_hw) -> list:
+  """The sub-pixel phases of a TRANSPOSE_CONV as a host list of (py, px, QH, QW, kys, kxs), py-major, for every phase
+  that has output pixels: the pixels oy = qy sh + py < OH (QH of them) and ox = qx sw + px < OW all use the taps
+  kys = (ky : (py + pad_top - ky) % sh == 0) and kxs likewise, in ascending order; tap ti of kys reads the input row
+  a = qy + (py + pad_top - kys[ti]) / sh. A stride above the kernel leaves phases with no tap (kys or kxs empty).
+  The geometry is tconv_geometry's."""
+  (sh, sw), (oh, ow) = _pair(stride, "stride"), _pair(out_hw, "out_hw")
+  top, left = tconv_geometry(ih, iw, kh, kw, (sh, sw), padding, (oh, ow))
+  out = []
+  for py in range(min(sh, oh)):
+    kys = tuple(range((py + top) % sh, int(kh), sh))
+    for px in range(min(sw, ow)):
+      kxs = tuple(range((px + left) % sw, int(kw), sw))
+      out.append((py, px, -(-(oh - py) // sh), -(-(ow - px) // sw), kys, kxs))
+  return out
+
+
+def _tconv_phase(x, kh: int, kw: int, stride, padding, out_hw, phase):
+  """(QH, QW, kys, kxs) of `phase` = (py, px) for x [N, IH, IW, C]; ValueError when the phase is none of the op's."""
+  py, px = _pair(phase, "phase")
+  for p in tconv_phases(int(x.shape[1]), int(x.shape[2]), kh, kw, stride, padding, out_hw):
+    if p[:2] == (py, px):
+      return p[2:]
+  raise ValueError(f"phase ({py}, {px}) is outside the strides {_pair(stride, 'stride')}, or has no output pixel in"
+                   f" {_pair(out_hw, 'out_hw')}")
+
+
+def tconv_patches(x: torch.Tensor, kh: int, kw: int, stride, padding, out_hw, phase, pad_value=0, first: int = 0,
+                  count: int | None = None) -> torch.Tensor:
+  """The patch rows of one phase of a TRANSPOSE_CONV: x [N, IH, IW, C] (int8, int16 or float32, on the device) ->
+  [count, |kys| |kxs| C] of the same dtype, rows first .. first + count - 1 of the N QH QW rows of `phase` = (py, px)
+  (default: all from `first` on), row t = (n, qy, qx) in that order and column (ti |kxs| + tj) C + c the tap
+  (kys[ti], kxs[tj]), channel c, read at a = qy + (py + pad_top - ky) / sh and b likewise; a tap outside the image
+  holds `pad_value`. The phases are tconv_phases', the geometry tconv_geometry's. A byte copy: a NaN pad keeps its
+  payload. The rows are what qfc_forward / qfc_forward_i16 / qfc_output read against the filter slice
+  W[:, kys][:, :, kxs] viewed as [O, |kys| |kxs| C]; the result is the output pixels (qy sh + py, qx sw + px).
+  A phase without a tap raises ValueError. Does not synchronize."""
+  rt.require_gpu()
+  if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in _CONV_DTYPES:
+    raise TypeError(f"expected an int8, int16 or float32 device tensor, got {getattr(x, 'dtype', type(x))}"
+                    f" on {getattr(x, 'device', 'the host')}")
+  if x.dim() != 4:
+    raise ValueError(f"expected an [N, IH, IW, C] tensor, got {tuple(x.shape)}")
+  n_img, h, w, c = (int(v) for v in x.shape)
+  if min(n_img, h, w, c) < 1:
+    raise ValueError(f"every dimension of x must be positive, got {tuple(x.shape)}")
+  kh, kw = int(kh), int(kw)
+  (sh, sw), (oh, ow), (py, px) = _pair(stride, "stride"), _pair(out_hw, "out_hw"), _pair(phase, "phase")
+  top, left = tconv_geometry(h, w, kh, kw, (sh, sw), padding, (oh, ow))
+  qh, qw, kys, kxs = _tconv_phase(x, kh, kw, (sh, sw), padding, (oh, ow), (py, px))
+  if not kys or not kxs:
+    raise ValueError(f"phase ({py}, {px}) has no tap: a stride of {sh}, {sw} exceeds the {kh} x {kw} kernel")
+  k = len(kys) * len(kxs) * c
+  if k > QFC_MAX_D:
+    raise ValueError(f"K = {len(kys)} x {len(kxs)} x {c} = {k} exceeds {QFC_MAX_D}, the forward entries' limit")
+  rows_all = n_img * qh * qw
+  if rows_all > 0x7FFFFFFF:
+    raise ValueError(f"{rows_all} patch rows exceed INT32_MAX")
+  first = int(first)
+  count = rows_all - first if count is None else int(count)
+  if first < 0 or count < 0 or first + count > rows_all:
+    raise ValueError(f"rows [{first}, {first} + {count}) are outside the {rows_all} patch rows of the phase")
+  pad_bytes = _pad_element(pad_value, _CONV_DTYPES[x.dtype])
+  if not x.is_contiguous():
+    x = x.contiguous()
+  out = rt.empty((count, k), x.dtype)
+  _ffi.check(_ffi.lib().mi355q_tconv_patches_nhwc(rt.ptr(x), x.element_size(), n_img, h, w, c, kh, kw, sh, sw, top, left,
+                                                  oh, ow, py, px, first, count, ctypes.cast(pad_bytes, ctypes.c_void_p),
+                                                  rt.ptr(out), rt.stream_ptr()))
+  return out
+
+
+def _tconv_filter_slices(who: str, w, o: int, kh: int, kw: int, c: int, phases: list) -> list:
+  """The filter slice W[:, kys][:, :, kxs] viewed [O, |kys| |kxs| C] of every phase: float32 tensors of a float32
+  filter, CompareTargets (per tensor, or per channel along dimension 0: slicing leaves the scales as they are) of an
+  int8 CompareTarget. Torch indexing: plumbing."""
+  n = o * kh * kw * c
+  if isinstance(w, CompareTarget):
+    if w.kind != "i8" or w.n != n or w.data.dtype != torch.int8 or not w.data.is_cuda:
+      raise ValueError(f"{who} needs an i8 filter of {o} x {kh} x {kw} x {c} elements on the device, got {w.kind!r} with {w.n}")
+    if w.zero_point is not None and bool(torch.any(w.zero_point != 0)):
+      raise ValueError("the weight's zero point must be 0")
+    if not (w.channels == 1 or (w.channels == o and w.inner == kh * kw * c)) or w.scale.numel() != w.channels:
+      raise ValueError(f"{who}: scale view ({w.channels} channels, inner {w.inner}) is neither per tensor nor per channel"
+                       f" along dimension 0 of a [{o}, {kh}, {kw}, {c}] filter")
+    data = w.data.view(o, kh, kw, c)
+  else:
+    if not isinstance(w, torch.Tensor) or not w.is_cuda or w.dtype != torch.float32 or w.numel() != n:
+      raise TypeError(f"{who}: expected a float32 device filter of {o} x {kh} x {kw} x {c} elements, got"
+                      f" {getattr(w, 'dtype', type(w))} {tuple(getattr(w, 'shape', ()))}")
+    data = w.contiguous().view(o, kh, kw, c)
+  out = []
+  for _, _, _, _, kys, kxs in phases:
+    if not kys or not kxs:
+      raise ValueError(f"{who}: a phase has no tap (a stride exceeds the {kh} x {kw} kernel)")
+    part = data[:, list(kys)][:, :, list(kxs)].reshape(o, -1).contiguous()
+    if isinstance(w, CompareTarget):
+      part = CompareTarget(part, part.numel(), "i8", w.scale, None, w.channels, part.shape[1] if w.channels == o else 1)
+    out.append(part)
+  return out
+
+
+def _tconv_run(who: str, x, dtypes, w, kh: int, kw: int, stride, padding, out_hw, pad_value, phase_fn, results: int):
+  """The whole op by phases: `phase_fn(rows, filter slice, image index of every row)` returns `results` tensors
+  [N QH QW, O] per phase, which are interleaved into `results` NHWC tensors [N, OH, OW, O] (out[:, py::sh, px::sw])."""
+  if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype not in dtypes:
+    names = " or ".join(str(t).replace("torch.", "") for t in dtypes)
+    raise TypeError(f"{who}: expected an {names} device tensor, got {getattr(x, 'dtype', type(x))}"
+                    f" on {getattr(x, 'device', 'the host')}")
+  if x.dim() != 4 or min(int(v) for v in x.shape) < 1:
+    raise ValueError(f"{who}: expected an [N, IH, IW, C] tensor with positive dimensions, got {tuple(x.shape)}")
+  n_img, h, wd, c = (int(v) for v in x.shape)
+  kh, kw = int(kh), int(kw)
+  (sh, sw), (oh, ow) = _pair(stride, "stride"), _pair(out_hw, "out_hw")
+  phases = tconv_phases(h, wd, kh, kw, (sh, sw), padding, (oh, ow))
+  n_w = w.n if isinstance(w, CompareTarget) else int(getattr(w, "numel", lambda: 0)())
+  if n_w < 1 or n_w % (kh * kw * c):
+    raise ValueError(f"{who}: the filter's {n_w} elements are no multiple of {kh} x {kw} x {c}")
+  o = n_w // (kh * kw * c)
+  slices = _tconv_filter_slices(who, w, o, kh, kw, c, phases)
+  outs = None
+  for (py, px, qh, qw, _, _), part in zip(phases, slices):
+    rows = tconv_patches(x, kh, kw, (sh, sw), padding, (oh, ow), (py, px), pad_value)
+    image = torch.arange(n_img * qh * qw, device=x.device) // (qh * qw)
+    got = phase_fn(rows, part, image)
+    if outs is None:
+      outs = [rt.empty((n_img, oh, ow, o), g.dtype) for g in got]
+    for full, g in zip(outs, got):
+      full[:, py::sh, px::sw, :] = g.view(n_img, qh, qw, o)
+  return outs[0] if results == 1 else tuple(outs)
+
+
+def tconv_forward(x: torch.Tensor, w, kh: int, kw: int, stride, padding, out_hw, x_scale: torch.Tensor | None = None,
+                  x_zero_point: int = 0, want_acc: bool = False):
+  """The TRANSPOSE_CONV product of an NHWC activation x [N, IH, IW, C] on the device and a filter [O, KH, KW, C], as
+  float32 NHWC [N, OH, OW, O] with `out_hw` = (OH, OW):
+    out[n, oy, ox, o] = Sum_{ky, kx, c} x[n, a, b, c] W[o, ky, kx, c]
+  over the taps with (oy + pad_top - ky) % sh == 0 and a = (oy + pad_top - ky) / sh in [0, IH), likewise b; the
+  geometry is tconv_geometry's (the forward convolution from OH x OW back to IH x IW; no dilation). Executed by
+  sub-pixel phases (tconv_phases): the rows of tconv_patches against the filter slice W[:, kys][:, :, kxs], so that
+  every multiply is a real one. By the dtype of x:
+    float32  `w` a float32 device tensor of O KH KW C elements: every phase is gemm(rows, slice^T);
+    int8     `w` a CompareTarget of kind i8 (per tensor, or per channel along dimension 0), `x_scale` float32 with 1
+             or N entries (one per IMAGE), `x_zero_point` in int8, which is also the pad element: every phase is
+             qfc_forward, y = float(Sum (x - zp_x) q_w) * (x_scale * w_scale), the accumulator exact in int32;
+    int16    as int8 without a zero point: qfc_forward_i16, the accumulator exact in int64.
+  Returns y, or (y, acc int32 / int64 [N, OH, OW, O]) with `want_acc` (integer activations only). The pre-bias
+  product. A stride above the kernel (a phase without a tap) raises ValueError. This is the library's own definition,
+  modelled on LiteRT's TRANSPOSE_CONV and unchecked against it. include/mi355q.h, "Patch gather for TRANSPOSE_CONV".
+  Does not synchronize."""
+  rt.require_gpu()
+  who = "tconv_forward"
+  is_float = isinstance(x, torch.Tensor) and x.dtype == torch.float32
+  if is_float:
+    if want_acc or x_scale is not None or int(x_zero_point) != 0:
+      raise ValueError(f"{who}: a float32 activation takes no x_scale, x_zero_point or want_acc")
+    return _tconv_run(who, x, (torch.float32,), w, kh, kw, stride, padding, out_hw, 0.0,
+                      lambda rows, part, image: (gemm(rows, part, trans_b=True),), 1)
+  if not isinstance(w, CompareTarget):
+    raise ValueError(f"{who} needs an i8 filter (a CompareTarget) for an integer activation, got {type(w)}")
+  if x_scale is None:
+    raise ValueError(f"{who}: an integer activation needs x_scale")
+  x_scale = _f32(x_scale).view(-1)
+  if isinstance(x, torch.Tensor) and x.dim() == 4 and x_scale.numel() not in (1, int(x.shape[0])):
+    raise ValueError(f"{who}: x_scale needs 1 or N = {int(x.shape[0])} entries (got {x_scale.numel()})")
+  int16 = isinstance(x, torch.Tensor) and x.dtype == torch.int16
+  zp = int(x_zero_point)
+  if (int16 and zp != 0) or not -128 <= zp <= 127:
+    raise ValueError(f"{who}: x_zero_point {x_zero_point} is outside int8, or given for an int16 activation")
+
+  def phase(rows, part, image):
+    scale = x_scale if x_scale.numel() == 1 else x_scale[image]
+    o, k = part.data.shape
+    if int16:
+      got = qfc_forward_i16(rows, scale, part, o, k, want_acc=want_acc)
+    else:
+      got = qfc_forward(rows, scale, zp, part, o, k, want_acc=want_acc)
+    return got if want_acc else (got,)
+  return _tconv_run(who, x, (torch.int8, torch.int16), w, kh, kw, stride, padding, out_hw, zp, phase, 2 if want_acc else 1)
+
+
+def tconv_output(x: torch.Tensor, x_zero_point: int, target: CompareTarget, kh: int, kw: int, stride, padding, out_hw,
+                 bias, multiplier, shift, out_zero_point: int, act_min: int, act_max: int) -> torch.Tensor:
+  """What a static int8 TRANSPOSE_CONV op stores: int8 NHWC [N, OH, OW, O] =
+  clamp(mbqm32(sat32(acc + bias), M, s) + out_zero_point, act_min, act_max) of tconv_forward's int32 accumulator,
+  out[n, oy, ox, o] = Sum_{ky, kx, c} (x[n, a, b, c] - x_zero_point) q_w[o, ky, kx, c] over the taps with
+  (oy + pad_top - ky) % sh == 0 and a = (oy + pad_top - ky) / sh in [0, IH), likewise b; with the arithmetic and the
+  argument forms of qfc_output (`bias` None or int32 [O]; `multiplier` / `shift` host tables of 1 or O entries, or
+  qfc_multipliers' result with `shift` None), which runs unchanged on every phase's rows. This is the library's own
+  definition, modelled on LiteRT's TRANSPOSE_CONV and unchecked against it. Does not synchronize."""
+  rt.require_gpu()
+  who = "tconv_output"
+  if not isinstance(target, CompareTarget):
+    raise ValueError(f"{who} needs an i8 filter (a CompareTarget), got {type(target)}")
+  zp = int(x_zero_point)
+  if not -128 <= zp <= 127:
+    raise ValueError(f"{who}: x_zero_point {x_zero_point} is outside int8")
+  tables = [None]
+
+  def phase(rows, part, image):
+    o, k = part.data.shape
+    if tables[0] is None:      # (checked and uploaded once for all phases)
+      tables[0] = (_qfc_output_tables(who, multiplier, shift, o, 8), _dwconv_bias(who, bias, o, torch.int32))
+    return (qfc_output(rows, zp, part, o, k, tables[0][1], tables[0][0], None, out_zero_point, act_min, act_max),)
+  return _tconv_run(who, x, (torch.int8,), target, kh, kw, stride, padding, out_hw, zp, phase, 1)
+
+
+def tconv_output_i16(x: torch.Tensor, target: CompareTarget, kh: int, kw: int, stride, padding, out_hw, bias, multiplier,
+                     shift, act_min: int, act_max: int) -> torch.Tensor:
+  """What a static int16-activation TRANSPOSE_CONV op stores: int16 NHWC [N, OH, OW, O], qfc_output_i16's arithmetic
+  on tconv_forward's int64 accumulator, out[n, oy, ox, o] = Sum_{ky, kx, c} x[n, a, b, c] q_w[o, ky, kx, c] over the
+  taps with (oy + pad_top - ky) % sh == 0 and a = (oy + pad_top - ky) / sh in [0, IH), likewise b (`bias` None or int64
+  [O]; shifts in [-31, 14]; no zero points). The library's own definition, modelled on LiteRT's TRANSPOSE_CONV and
+  unchecked against it. Does not synchronize."""
+  rt.require_gpu()
+  who = "tconv_output_i16"
+  if not isinstance(target, CompareTarget):
+    raise ValueError(f"{who} needs an i8 filter (a CompareTarget), got {type(target)}")
+  tables = [None]
+
+  def phase(rows, part, image):
+    o, k = part.data.shape
+    if tables[0] is None:
+      tables[0] = (_qfc_output_tables(who, multiplier, shift, o, 16), _dwconv_bias(who, bias, o, torch.int64))
+    return (qfc_output_i16(rows, part, o, k, tables[0][1], tables[0][0], None, act_min, act_max),)
+  return _tconv_run(who, x, (torch.int16,), target, kh, kw, stride, padding, out_hw, 0, phase, 1)
 
 
 # (include/mi355q.h, "Direct depthwise convolution")

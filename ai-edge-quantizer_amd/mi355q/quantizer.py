@@ -251,7 +251,8 @@ class Quantizer:
                                quantized_outputs: bool = False,
                                conv_2d: bool = False,
                                depthwise_conv_2d: bool = False,
-                               batch_matmul: bool = False) -> model_validator.LayerExecutionComparison:
+                               batch_matmul: bool = False,
+                               transpose_conv: bool = False) -> model_validator.LayerExecutionComparison:
     """Executes every quantized FULLY_CONNECTED op of the last quantize() result in integers on the calibration
     samples and compares it with the float product: error = (1/n) ||Yq - Y||^2 per op with its signal, MSE, SNR,
     per-channel errors, token count and mode (model_validator.compare_layer_execution). Unlike
@@ -275,7 +276,10 @@ class Quantizer:
     `batch_matmul` every BATCH_MATMUL op is executed too, by the integer batched product (ops.qbmm_forward): a constant
     right-hand side in the static, dynamic and weight-only modes, or two INT8 activations with a zero point each (the
     attention products); an entry has `op` = "BATCH_MATMUL", `operands`, `adj_x`, `adj_y` and `batch`, `rows` = N and
-    `d` = K (model_validator.compare_layer_execution)."""
+    `d` = K. With `transpose_conv` every TRANSPOSE_CONV op is executed too, by sub-pixel phases on patch rows
+    (ops.tconv_patches), so that no multiply meets a stuffed zero: an entry has the keys of a conv entry without
+    `dilations`, with `op` = "TRANSPOSE_CONV", `tokens` the output pixels and `phases`
+    (model_validator.compare_layer_execution)."""
     quantized_model = self._result.quantized_model
     if quantized_model is None:
       raise ValueError("No quantized model available to validate.")
@@ -284,7 +288,8 @@ class Quantizer:
                                                       follow_input_transforms=follow_input_transforms,
                                                       int16_activations=int16_activations,
                                                       quantized_outputs=quantized_outputs, conv_2d=conv_2d,
-                                                      depthwise_conv_2d=depthwise_conv_2d, batch_matmul=batch_matmul)
+                                                      depthwise_conv_2d=depthwise_conv_2d, batch_matmul=batch_matmul,
+                                                      transpose_conv=transpose_conv)
     if save_folder:
       if model_name is None:
         model_name = pathlib.Path(self._model_name).stem if self._model_name else "model"

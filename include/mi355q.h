@@ -1177,6 +1177,58 @@ int32_t mi355q_conv_patches_nhwc(const void* x, int32_t elem_bytes, int64_t N, i
                                  int64_t row_count, const void* pad_element, void* out, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * Patch gather for TRANSPOSE_CONV (csrc/conv_patches.hip): one sub-pixel
+ * phase of a transposed convolution as the rows the integer FULLY_CONNECTED
+ * entries read. A TFLite TRANSPOSE_CONV of x [N, IH, IW, C] with a filter
+ * [O, KH, KW, C] and strides (sh, sw) writes out [N, OH, OW, O],
+ *   out[n, oy, ox, o] = Sum_{ky, kx, c} x[n, a, b, c] W[o, ky, kx, c]
+ * over the taps with (oy + pad_top - ky) % sh == 0, a = (oy + pad_top - ky) / sh
+ * in [0, IH), and likewise b from ox, pad_left, kx and sw. (pad_top, pad_left)
+ * is the padding of the FORWARD convolution from [OH, OW] back to [IH, IW]
+ * (TFLite's rule, no dilation). The output pixels of one phase (py, px),
+ * oy = qy sh + py and ox = qx sw + px, all use the same taps
+ *   kys = {ky : (py + pad_top - ky) % sh == 0} = ry, ry + sh, ... < KH
+ *   kxs likewise,   ry = (py + pad_top) % sh
+ * so the phase is an ordinary product of its patch rows with the filter slice
+ * W[:, kys][:, :, kxs] viewed as [O, |kys| |kxs| C], and the phases together
+ * multiply no hole: a gather of full KH KW C rows over a zero-stuffed input
+ * would multiply sh sw - 1 of every sh sw taps by nothing.
+ *
+ * Statement. With QH = ceil((OH - py) / sh), QW = ceil((OW - px) / sw),
+ * TH = |kys|, TW = |kxs|, K = TH TW C, by = (py + pad_top) / sh and
+ * bx = (px + pad_left) / sw (integer divisions, on the host), for
+ * t in [first_row, first_row + row_count):
+ *   n = t / (QH QW)      qy = (t / QW) % QH      qx = t % QW
+ * and for k = (ti TW + tj) C + c  (tap ky = ry + ti sh, kx = rx + tj sw):
+ *   a = qy + by - ti      b = qx + bx - tj
+ *   out[(t - first_row) K + k] = x[((n IH + a) IW + b) C + c]
+ *                                          when 0 <= a < IH and 0 <= b < IW
+ *                              = *pad_element                    otherwise
+ * Elements, pad_element, the byte copy, the two routes, the 64-bit index
+ * arithmetic and the window are those of the CONV_2D gather above, and so is
+ * the kernel: the phase is its stride-1 gather with a dilation of -1. Whatever
+ * the arguments, no element outside x is read.
+ *
+ * Refused before any launch: elem_bytes outside {1, 2, 4}; N, IH, IW, C, KH,
+ * KW, OH, OW or a stride that is not positive; a phase outside
+ * [0, stride_h) x [0, stride_w); a negative first_row or row_count
+ * (MI355Q_BAD_ARG); N, IH, IW, OH or OW above INT32_MAX (MI355Q_UNSUPPORTED);
+ * a geometry whose forward convolution does not map [OH, OW] to [IH, IW]: per
+ * axis IH = ceil(OH / sh) (SAME) or IH = (OH + sh - KH) / sh (VALID), and
+ * pad_top = max(0, (IH - 1) sh + KH - OH) / 2 (MI355Q_BAD_ARG); a phase with no
+ * tap, ry >= KH, which a stride above the kernel leaves (MI355Q_UNSUPPORTED);
+ * K > 65536; N QH QW > INT32_MAX (MI355Q_UNSUPPORTED); first_row + row_count >
+ * N QH QW (MI355Q_BAD_ARG; a phase with py >= OH has no rows). Those limits
+ * keep the activation far below the 2^62 bytes of the CONV_2D entry. After
+ * those row_count == 0 enqueues nothing; otherwise a null x, out or
+ * pad_element is MI355Q_BAD_ARG.
+ * ------------------------------------------------------------------------ */
+int32_t mi355q_tconv_patches_nhwc(const void* x, int32_t elem_bytes, int64_t N, int64_t IH, int64_t IW, int64_t C, int32_t KH,
+                                  int32_t KW, int32_t stride_h, int32_t stride_w, int32_t pad_top, int32_t pad_left,
+                                  int64_t OH, int64_t OW, int32_t phase_h, int32_t phase_w, int64_t first_row,
+                                  int64_t row_count, const void* pad_element, void* out, void* stream);
+
+/* ---------------------------------------------------------------------------
  * Direct depthwise convolution (csrc/dwconv.hip): the DEPTHWISE_CONV_2D op on
  * an NHWC activation, in float32 and in integers. A TFLite depthwise filter is
  * [1, KH, KW, O]: the reduction of an output channel is its KH KW taps alone,
