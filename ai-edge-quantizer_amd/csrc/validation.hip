@@ -33,7 +33,7 @@ namespace {
 
 constexpr int kChunk = 8192;          // NumPy nditer buffer size (elements)
 constexpr int kThreads = 256;
-constexpr int kMaxLeaves = 256;       // a chunk of <= 8192 elements has <= 137 pairwise leaves
+constexpr int kMaxLeaves = 256;       // a chunk of <= 8192 elements has <= 65 pairwise leaves (tests/compare_route_cases.py)
 constexpr int kBins1 = 2048;          // ratio bits 30..20
 constexpr int kBins2 = 2048;          // ratio bits 19..9
 constexpr int kBins3 = 512;           // ratio bits 8..0

@@ -78,6 +78,15 @@ def _world(group=None) -> tuple[int, int]:
   return dist.get_rank(group), dist.get_world_size(group)
 
 
+def first_rank_says(value, group=None):
+  """`value` as the group's first rank has it, on every rank (the value itself without a group of several ranks)."""
+  if _world(group)[1] == 1:
+    return value
+  box = [value]
+  dist.broadcast_object_list(box, src=0 if group is None else dist.get_global_rank(group, 0), group=group)
+  return box[0]
+
+
 def _comm_device(group=None) -> torch.device:
   if dist.is_initialized() and dist.get_backend(group) == "nccl":
     return torch.device("cuda", torch.cuda.current_device())

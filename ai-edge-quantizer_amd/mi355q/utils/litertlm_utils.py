@@ -379,7 +379,10 @@ def quantize_litertlm(litertlm_path: Path, recipe: Any, output_path: Path, overw
   its size, the other ranks return None. `stats` receives wall seconds per phase.
   """
   from .. import distributed
-  if os.path.exists(output_path) and not overwrite:
+  # The rank that writes the file asks whether it is there, and every rank takes its answer: that rank creates the file
+  # early in this very call (prepare_output, before the first collective), so a rank that arrives later and looked for
+  # itself would find it and raise alone, leaving the others in their collectives.
+  if distributed.first_rank_says(os.path.exists(output_path), group) and not overwrite:
     raise ValueError(f"The model {output_path} already exists. Specify overwrite=True to replace it.")
   import time
   src = LiteRTLMFile(litertlm_path)

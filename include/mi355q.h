@@ -794,7 +794,9 @@ int32_t mi355q_compare_f32(const float* reference, const void* target, int64_t n
                            void* workspace, size_t workspace_bytes, void* stream);
 /* `count` pairs in one set of launches; `pairs` is a DEVICE table, so its entries are checked on the device: when
  * an entry is invalid (as mi355q_compare_f32 would refuse it) or total_chunks is not Sum mi355q_compare_chunks(n_i),
- * no operand is read and every result of the call is NaN. */
+ * no operand is read and every float field of every result of the call is NaN. An entry with n = 0 is valid whatever its
+ * other fields hold: nothing of it is read, it takes no chunk, and its result is all zeros (a table of only such
+ * entries has total_chunks = 0). */
 int32_t mi355q_compare_f32_batched(const mi355q_compare_pair* pairs, int32_t count, int64_t total_chunks,
                                    int32_t flags, mi355q_compare_result* results, void* workspace,
                                    size_t workspace_bytes, void* stream);

@@ -370,6 +370,44 @@ def _run(worker, world=2, timeout=300):
   return sorted(results, key=lambda r: r[0])
 
 
+def _worker_output_exists(rank, world, port, out):
+  """quantize_litertlm on two ranks that see different things at the output path: as when the writing rank has created
+  the file (prepare_output) before the other rank arrives."""
+  import tempfile
+  dist = _setup(rank, world, port)
+  from mi355q import distributed as D
+  from mi355q.utils import litertlm_utils as L
+  said = D.first_rank_says(("rank", rank))
+  seen = []
+  with tempfile.TemporaryDirectory() as tmp:
+    there = os.path.join(tmp, "there.litertlm")
+    open(there, "wb").close()
+    missing = os.path.join(tmp, "missing.litertlm")
+    for writer_sees_it in (False, True):
+      path = there if (rank == 0) == writer_sees_it else missing
+      try:
+        L.quantize_litertlm(os.path.join(tmp, "no_such_source.litertlm"), [], path)
+        seen.append("no error")
+      except Exception as e:      # pylint: disable=broad-except
+        seen.append(f"{type(e).__name__}: {e}")
+      dist.barrier()
+  out.put((rank, said, seen))
+  dist.barrier()
+  dist.destroy_process_group()
+
+
+def test_every_rank_takes_the_writing_ranks_word_for_an_existing_output():
+  """The writing rank creates the output file before the first collective of the call: a rank that arrives later must
+  not find it and raise alone."""
+  (_, said0, seen0), (_, said1, seen1) = _run(_worker_output_exists)
+  assert said0 == said1 == ("rank", 0)
+  for seen in (seen0, seen1):
+    assert "already exists" not in seen[0] and seen[0] != "no error"      # both go on (to a source that is not there)
+    assert seen[1].startswith("ValueError") and "already exists" in seen[1]
+  from mi355q import distributed as D
+  assert D.first_rank_says("alone") == "alone"      # no process group: the value itself
+
+
 def test_sample_shard_and_plan():
   from mi355q import distributed as D
   assert [list(D.sample_shard(11, r, 2)) for r in range(2)] == [list(range(6)), list(range(6, 11))]
