@@ -14,11 +14,15 @@
 //                           through L1 / L2. Block 32 uses v_mfma_i32_16x16x32_i8 (8 bytes per lane). This file adds
 //                           the float rescale: blockwise scales flush the int32 tile into float32 sums after every
 //                           block, in ascending order, without FMA.
-//   qfc_generic_kernel      one thread per output, element by element: every other shape and alignment, same bits.
+//   (qfc_staged.hip)        stored I8 with per-tensor or per-channel scales at ANY other d and alignment: the same tile
+//                           and rescale (qfc_tile_out.h), both operands staged through LDS.
+//   qfc_generic_kernel      one thread per output, element by element: what neither serves (I4 / I2 or blockwise
+//                           scales at a ragged d or from a misaligned base), same bits.
 //   sqdiff_cols_*_kernel    per column Sum_t (a - b)^2 and Sum_t b^2 in float64 in a fixed order.
 #include "common.h"
 #include "compare_target.h"
 #include "qfc_tile.h"
+#include "qfc_tile_out.h"
 
 namespace mi355q {
 namespace {
@@ -121,28 +125,7 @@ __global__ __launch_bounds__(kThreads) void quantize_rows_scalar_kernel(const fl
 }
 
 // ---------------------------------------------------------------- the integer product
-struct FwdArgs {
-  const int8_t* xq;        // [n, d]
-  const uint8_t* w;        // [rows, d] stored
-  const float* x_scale;    // 1 or n
-  const float* w_scale;    // 1, rows or rows * nblocks
-  const int32_t* wsum;     // [rows, nblocks] (read only when zp != 0)
-  float* y;                // [n, rows]
-  int32_t* acc;            // [n, rows] or null
-  long long n, rows, d;
-  int x_per_row;           // x_scale has n entries
-  int w_mode;              // 0 per tensor, 1 per channel, 2 blockwise
-  int nblocks;             // blocks per weight row (1 unless blockwise)
-  int block;               // elements per block (d unless blockwise)
-  int zp;
-  int kind;
-};
-
-struct ChanF {
-  float sw;      // the channel's weight scale
-  int corr;      // zp * Sum_k q_w[r][k]
-};
-
+// (FwdArgs, and the float rescale of the scales that are not blockwise: qfc_tile_out.h, with qfc_staged.hip)
 template <int KIND, int KSTEP, bool BLOCKWISE>
 __global__ __launch_bounds__(kThreads) void qfc_mfma_kernel(FwdArgs g) {
   constexpr int TA = QfcTile<int8_t>::TA;
@@ -185,26 +168,13 @@ __global__ __launch_bounds__(kThreads) void qfc_mfma_kernel(FwdArgs g) {
           }
       }
     });
+    qfc_walk_outputs<int8_t>(
+        wv, g.n, g.rows, [](long long) { return 0; },
+        [=, &yf](int, int a, int b, int i, long long t, long long r) { g.y[t * g.rows + r] = yf[a][b][i]; });
   } else {
     qfc_main_loop<int8_t, KIND, KSTEP>(wv, g.xq, g.w, g.n, g.rows, g.d, acc);
+    qfc_store_float(g, wv, acc);
   }
-
-  qfc_walk_outputs<int8_t>(
-      wv, g.n, g.rows,
-      [=](long long r) {
-        if (BLOCKWISE) return ChanF{0.0f, 0};
-        return ChanF{g.w_scale[g.w_mode == 1 ? r : 0], g.zp != 0 ? g.zp * g.wsum[r] : 0};
-      },
-      [=, &acc, &yf](const ChanF& c, int a, int b, int i, long long t, long long r) {
-        if (BLOCKWISE) {
-          g.y[t * g.rows + r] = yf[a][b][i];
-        } else {
-          const int v = acc[a][b][i] - c.corr;
-          const float sc = g.x_scale[g.x_per_row ? t : 0] * c.sw;
-          g.y[t * g.rows + r] = static_cast<float>(v) * sc;
-          if (g.acc) g.acc[t * g.rows + r] = v;
-        }
-      });
 }
 
 // Generic route: one thread per output element, one weight element at a time.
@@ -360,8 +330,11 @@ extern "C" int32_t mi355q_qfc_forward_i8(const int8_t* xq, int64_t n, int64_t d,
     if (st_sums != MI355Q_OK) return st_sums;
   }
 
-  if (mfma_route(xq, w, d, blockwise && block == 32 ? 32 : 64))
+  const int64_t route = mi355q_qfc_route(xq, w, d, w_kind, block, blockwise ? 1 : 0);
+  if (route == MI355Q_QFC_ROUTE_MFMA)
     dispatch_kind(w_kind, [&](auto kind) { launch_mfma<decltype(kind)::value>(g, blockwise, grid, st); });
+  else if (route == MI355Q_QFC_ROUTE_STAGED)
+    launch_qfc_staged(g, grid, st);
   else
     hipLaunchKernelGGL(qfc_generic_kernel, dim3(generic_blocks(n * rows)), dim3(kThreads), 0, st, g);
   MI355Q_CHECK_LAUNCH("integer fully-connected launch");

@@ -9,13 +9,16 @@
 //                             multiplier and shift are read once per b and serve 16 outputs each.
 //   qfc_out16_mfma_kernel     the same loop for int16 activations (two int8 planes, 32 tokens x 64 channels per
 //                             wave), written out here as in qfc16.hip; combined with 128 Sum w in int64 in the epilogue.
+//   (qfc_staged.hip)          under int8, a stored I8 weight at any other d or alignment: the same tile and epilogue
+//                             (qfc_tile_out.h), both operands staged through LDS.
 //   qfc_out_generic_kernel,
-//   qfc_out16_generic_kernel  one thread per output, element by element: every other shape and alignment, same bits.
+//   qfc_out16_generic_kernel  one thread per output, element by element: what no MFMA route serves, same bits.
 // The two fixed-point epilogues are qfc_epilogue.h's (dwconv.hip runs them too); qfc.hip and qfc16.hip hold the float ones.
 #include "common.h"
 #include "compare_target.h"
 #include "qfc_epilogue.h"
 #include "qfc_tile.h"
+#include "qfc_tile_out.h"
 
 namespace mi355q {
 namespace {
@@ -29,17 +32,7 @@ __global__ __launch_bounds__(kThreads) void qfc_out_mfma_kernel(OutArgs g) {
   if (!qfc_wave<int8_t>(wv, g.n, g.rows)) return;
   I32x4 acc[QfcTile<int8_t>::TM][TB];
   qfc_main_loop<int8_t, KIND, 64>(wv, static_cast<const int8_t*>(g.xq), g.w, g.n, g.rows, g.d, acc);
-
-  struct Chan {
-    Chan8 c;
-    int corr;      // zp_x * Sum_k q_w[r][k]
-  };
-  int8_t* q = static_cast<int8_t*>(g.q);
-  qfc_walk_outputs<int8_t>(
-      wv, g.n, g.rows, [=](long long r) { return Chan{chan8(g, r), g.zp_x != 0 ? g.zp_x * g.wsum[r] : 0}; },
-      [=, &acc](const Chan& c, int a, int b, int i, long long t, long long r) {
-        q[t * g.rows + r] = output8(acc[a][b][i] - c.corr, c.c, g);
-      });
+  qfc_store_output8(g, wv, acc);      // (qfc_tile_out.h, with qfc_staged.hip)
 }
 
 // Generic route: one thread per output element, one weight element at a time.
@@ -208,14 +201,18 @@ extern "C" int32_t mi355q_qfc_output_i8(const int8_t* xq, int64_t n, int64_t d, 
   g.zp_x = x_zero_point; g.zp_y = out_zero_point; g.act_min = act_min; g.act_max = act_max; g.kind = w_kind;
   hipStream_t st = as_stream(stream);
 
-  if (mfma_route(xq, w, d, 64)) {
+  const int64_t route = mi355q_qfc_route(xq, w, d, w_kind, 0, 0);
+  if (route != MI355Q_QFC_ROUTE_GENERIC) {
     if (x_zero_point != 0) {
       const int32_t st_sums = launch_weight_sums(g.w, w_kind, rows, static_cast<long long>(d), static_cast<int32_t*>(workspace), st);
       if (st_sums != MI355Q_OK) return st_sums;
     }
-    dispatch_kind(w_kind, [&](auto kind) {
-      hipLaunchKernelGGL(qfc_out_mfma_kernel<decltype(kind)::value>, grid, dim3(kThreads), 0, st, g);
-    });
+    if (route == MI355Q_QFC_ROUTE_STAGED)
+      launch_qfc_out_staged(g, grid, st);
+    else
+      dispatch_kind(w_kind, [&](auto kind) {
+        hipLaunchKernelGGL(qfc_out_mfma_kernel<decltype(kind)::value>, grid, dim3(kThreads), 0, st, g);
+      });
   } else {      // (the generic kernel subtracts the zero point element by element: no weight sums)
     hipLaunchKernelGGL(qfc_out_generic_kernel, dim3(generic_blocks(n * rows)), dim3(kThreads), 0, st, g);
   }

@@ -136,6 +136,8 @@ PROTOTYPES = {
     "mi355q_qfc_forward_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
     "mi355q_qfc_forward_i8": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_i32, c_ptr, c_i32, c_i64, c_ptr, c_i64, c_i32,
                                       c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "mi355q_qfc_route": (c_i64, [c_ptr, c_ptr, c_i64, c_i32, c_i32, c_i32]),
+    "mi355q_qfc_set_staged": (c_i64, [c_i32]),
     "mi355q_qfc_forward_i16_workspace_bytes": (c_size, [c_i64, c_i64, c_i32]),
     "mi355q_qfc_forward_i16": (c_i32, [c_ptr, c_i64, c_i64, c_ptr, c_i64, c_ptr, c_i32, c_i64, c_ptr, c_i64, c_i32,
                                        c_ptr, c_ptr, c_ptr, c_size, c_ptr]),

@@ -1083,6 +1083,30 @@ def _qfc_block(who: str, xq: torch.Tensor, dtype, target: CompareTarget, rows: i
   return block
 
 
+QFC_ROUTES = ("generic", "mfma", "staged")      # MI355Q_QFC_ROUTE_*
+
+
+def qfc_route(xq, w, d: int, kind: str = "i8", block: int = 0, blockwise: bool = False) -> str:
+  """The kernel qfc_forward (and, with block = 0, qfc_output) takes for these operands: "mfma" (d a multiple of the
+  step from 16-byte aligned bases: fragments straight from memory), "staged" (a stored i8 weight with per-tensor or
+  per-channel scales at any other d or alignment: the same tile, operands staged through LDS) or "generic" (one
+  thread per output). `xq` and `w` are tensors or plain addresses; nothing is read or launched, no GPU is needed."""
+  a, b = (p if isinstance(p, int) else rt.ptr(p) for p in (xq, w))
+  return QFC_ROUTES[_ffi.lib().mi355q_qfc_route(a, b, int(d), COMPARE_KINDS[kind], int(block), int(bool(blockwise)))]
+
+
+@_contextlib.contextmanager
+def qfc_staged(enabled: bool = True):
+  """Inside this block the staged route of qfc_forward / qfc_output is on (the default everywhere) or off: off, its
+  shapes run on the generic kernel, as they did before the route existed, with the same bits. Process-wide."""
+  L = _ffi.lib()
+  before = L.mi355q_qfc_set_staged(int(bool(enabled)))
+  try:
+    yield
+  finally:
+    L.mi355q_qfc_set_staged(int(before))
+
+
 def qfc_forward(xq: torch.Tensor, x_scale: torch.Tensor, x_zero_point: int, target: CompareTarget, rows: int, d: int,
                 want_acc: bool = False):
   """The integer FULLY_CONNECTED product of int8 activations xq [n, d] and the stored integer weight [rows, d] of

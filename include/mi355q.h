@@ -965,9 +965,24 @@ int32_t mi355q_requant_delta_sweep_f32(const float* x, int64_t rows, int64_t col
  * weight is written to memory. Block 32 uses v_mfma_i32_16x16x32_i8 with 8
  * consecutive bytes per lane. A wave owns 64 tokens x 64 channels (4 x 4 MFMA
  * tiles: 8 fragment loads feed 16 MFMAs, the next step's loads in flight), a
- * workgroup 128 x 128. Generic route (every other d, e.g. odd d with packed
- * weights whose rows begin inside a byte, and misaligned xq or w): one thread
- * per output, one element at a time, the same bits.
+ * workgroup 128 x 128. Staged route (w_kind I8 with per-tensor or per-channel
+ * scales, at every other d >= 1 and every byte alignment of xq and w): the same
+ * tile and the same MFMA, both operands copied through LDS in stages of 64
+ * bytes of d with aligned 4-byte loads and a per-row byte shift, zero beyond d,
+ * n and rows; the same bits. Generic route (what is left: I4 / I2 weights or
+ * blockwise scales at a d that is no multiple of the step, e.g. odd d with
+ * packed weights whose rows begin inside a byte, or from a misaligned xq or w):
+ * one thread per output, one element at a time, the same bits.
+ *
+ * mi355q_qfc_route: which of the three mi355q_qfc_forward_i8 takes for these
+ * addresses (never read), d, w_kind, block and blockwise != 0 (w_scale_count ==
+ * rows * d / block); mi355q_qfc_output_i8 takes the same with block = blockwise
+ * = 0. MI355Q_QFC_ROUTE_GENERIC, _MFMA or _STAGED. Host only: it launches
+ * nothing and records no error. mi355q_qfc_set_staged(0) takes the staged route
+ * away (its shapes run on the generic kernel, as they did before the route
+ * existed: an A/B in one process), anything else gives it back; it returns the
+ * setting it replaced. Process-wide, on by default. (Queries and a switch, not
+ * statuses: int64_t, as mi355q_qbmm_mfma_route is.)
  *
  * Refused before any launch: negative shapes, null xq / x_scale / w / w_scale /
  * y_out, another w_kind, x_zero_point outside int8, block outside {0, 32, 64,
@@ -997,6 +1012,11 @@ int32_t mi355q_qfc_forward_i8(const int8_t* xq, int64_t n, int64_t d, const floa
                               int32_t x_zero_point, const void* w, int32_t w_kind, int64_t rows, const float* w_scale,
                               int64_t w_scale_count, int32_t block, float* y_out, int32_t* acc_out, void* workspace,
                               size_t workspace_bytes, void* stream);
+#define MI355Q_QFC_ROUTE_GENERIC 0
+#define MI355Q_QFC_ROUTE_MFMA 1
+#define MI355Q_QFC_ROUTE_STAGED 2
+int64_t mi355q_qfc_route(const void* xq, const void* w, int64_t d, int32_t w_kind, int32_t block, int32_t blockwise);
+int64_t mi355q_qfc_set_staged(int32_t enabled);
 size_t mi355q_sqdiff_cols_workspace_bytes(int64_t n, int64_t cols);
 int32_t mi355q_sqdiff_cols_f64(const float* a, const float* b, int64_t n, int64_t cols, double* sq_diff_cols,
                                double* sq_b_cols, int32_t accumulate, void* workspace, size_t workspace_bytes,
@@ -1111,8 +1131,10 @@ int32_t mi355q_qfc_forward_i16(const int16_t* xq, int64_t n, int64_t d, const fl
  * runs on the accumulator tile IN REGISTERS and only q_out is stored: no
  * [n, rows] accumulator or float array is written to memory. In the C / D map a
  * lane's values of a tile column all belong to channel l & 15, so bias,
- * multiplier and shift are read once per 16-channel tile and lane. Every other
- * d or alignment: one thread per output, the same bits.
+ * multiplier and shift are read once per 16-channel tile and lane. Under int8
+ * a stored I8 weight at every other d or alignment takes the forward entry's
+ * staged route (mi355q_qfc_route with block = blockwise = 0) into the same
+ * epilogue. What is left: one thread per output, the same bits.
  *
  * Refused before any launch, with the forward entries' texts where they overlap:
  * negative shapes, null xq / w / multiplier / shift / q_out, another w_kind,
